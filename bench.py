@@ -14,11 +14,21 @@ consecutive groups alternate between two HIP streams: modem_chain_batch_*, DESIG
 back-to-back steps: the device clock dips for the first ~100 ms of sustained load, and the
 driver's 20-step region (~1.2 ms) would otherwise measure that transient (tools/region_probe.py).
 
-Also reported: the dominant kernel's HBM roofline (algorithmic bytes per launch / its mean
-duration from HIP events on the launch stream; peak 8 TB/s), the whole chain's roofline,
-and the CPU oracle (the reference loop restated in C) timed on a bounded sample on rank 0.
+A plain run does only that: it sets up, settles, warms up, times --steps steps and prints the
+JSON line (`value`, `ms_per_step`, the workload). The settling steps run on a twin of the runner
+(its buffers, handles of its own), so the timed handles enter the warmup fresh and step W + N
+computes the same arrays in every run; `--dump-outputs DIR` writes them (the TX samples, the
+RX's decimated I/Q and decisions of every channel, float32, a fixed seeded sample of the rows
+of an array over its share of 48 MiB) as DIR/<name>.npy.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5|c5h]
+With --full also reported, from runs of their own after the timed steps: the decisions checked
+against the symbols sent, the host gather of the decisions, the dominant kernel's HBM roofline
+(algorithmic bytes per launch / its mean duration from HIP events on the launch stream; peak
+8 TB/s), the whole chain's roofline, C5 f32 as the out-of-cache roofline beside a C3 line, and
+the CPU oracle (the reference loop restated in C) timed on a bounded sample on rank 0.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5|c5h] [--full]
+                    [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -36,6 +46,7 @@ import numpy as np  # noqa: E402
 METRIC = "Msamples/s through TX+RX chain (129-tap RRC, f32 I/Q); % HBM roofline"
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 SEED = 0x5EED0000
+DUMP_BYTES = 48 << 20          # --dump-outputs: float32 bytes over all arrays of all ranks (< 64 MB of files)
 
 # name: (phasor, bps, ntaps, sps, samples per channel, channels per GPU, dtype, description)
 WORKLOADS = {
@@ -90,12 +101,13 @@ def channel_seed(rank, nch, c):
 class GpuRunner:
     """The product path: rust_modem_amd handles on this rank's GPU, buffers resident in HBM."""
 
-    def __init__(self, wl, rank, device, streams=1, batch=False, amplitude=1.0, group=0):
+    def __init__(self, wl, rank, device, streams=1, batch=False, amplitude=1.0, group=0, share=None):
         import torch
         import __graft_entry__ as g
         self.torch = torch
         m = g.package()
         self._m = m
+        self._args = (wl, rank, device, streams, batch, amplitude, group)
         name, bps, L, sps, nsamp, nch, dtype, _ = wl
         self.bps, self.L, self.sps, self.nsamp, self.nch, self.dtype = bps, L, sps, nsamp, nch, dtype
         torch.cuda.set_device(device)
@@ -116,7 +128,7 @@ class GpuRunner:
         nbits = nsamp // sps * bps
         for c in range(nch):
             seed = channel_seed(rank, nch, c)
-            bits = m.prng_bits(seed, nbits, device=device)
+            bits = share.ch[c]["bits"] if share is not None else m.prng_bits(seed, nbits, device=device)
             tx = m.DigitalModulator(m.Carrier(w), ph(), sps, taps, dtype=dtype, device=device)
             rx = m.DemodulatorRx(m.Carrier(w), taps, decim=sps, decim_offset=L - 1, mix=m.MIX_COMPLEX,
                                  slicer=ph().slicer(), in_dtype=dtype, out_dtype=dtype, device=device)
@@ -124,10 +136,13 @@ class GpuRunner:
             # tests would otherwise hide a handle left on device 0)
             assert tx.device == device and rx.device == device, (tx.device, rx.device, device)
             tdt = torch.float16 if dtype == 1 else torch.float32
-            y = torch.empty((nsamp, 2), dtype=tdt, device=f"cuda:{device}")
             nout = rx.noutputs(nsamp)
-            oiq = torch.empty((nsamp // sps, 2), dtype=tdt, device=f"cuda:{device}")
-            osym = torch.empty(nsamp // sps, dtype=torch.uint8, device=f"cuda:{device}")
+            if share is not None:     # a settle twin runs over the buffers of the runner it settles for
+                y, oiq, osym = (share.ch[c][k] for k in ("y", "oiq", "osym"))
+            else:
+                y = torch.empty((nsamp, 2), dtype=tdt, device=f"cuda:{device}")
+                oiq = torch.empty((nsamp // sps, 2), dtype=tdt, device=f"cuda:{device}")
+                osym = torch.empty(nsamp // sps, dtype=torch.uint8, device=f"cuda:{device}")
             self.ch.append(dict(bits=bits, tx=tx, rx=rx, y=y, oiq=oiq, osym=osym, nout=nout))
         if batch:       # prepared batch calls over the fixed per-channel buffers
             # groups of `group` channels (all of them when 0): the step runs each group's TX
@@ -196,6 +211,43 @@ class GpuRunner:
 
     def sync(self):
         self.torch.cuda.synchronize()
+
+    def settle_twin(self):
+        """A second runner of the same configuration over this runner's device buffers, with
+        handles of its own, for the untimed clock-settling steps: how many of those fit their
+        wall-time budget differs from run to run, and a handle's output depends on how many
+        samples it has produced (the carrier phase is a function of the f32 sample counter).
+        With the twin settling, this runner's handles enter the warmup fresh, so the step
+        after W + N steps computes the same arrays in every run (--dump-outputs)."""
+        return GpuRunner(*self._args, share=self)
+
+    def last_nout(self, c):
+        """Kept instants channel c's last RX call produced (DemodulatorRx.noutputs of that call:
+        the first call of a stream produces (L - 1) / sps fewer than the later ones)."""
+        rx = self.ch[c]["rx"]
+        end = rx.carrier.sample
+
+        def first(x):
+            return 0 if x <= rx.decim_offset else (x - rx.decim_offset + rx.decim - 1) // rx.decim
+        return first(end) - first(end - self.nsamp)
+
+    def outputs(self, budget):
+        """What the last step handed its caller, per channel: the TX's samples, the RX's decimated
+        I/Q and its decisions, as (name, float32 host array) pairs of at most `budget` bytes in
+        all. An array over its share is cut to a fixed, seeded sample of its rows (ascending)."""
+        torch = self.torch
+        per = budget // (3 * self.nch)
+        out = []
+        for c, d in enumerate(self.ch):
+            k = self.last_nout(c)
+            for name, t in (("tx_samples", d["y"]), ("rx_iq", d["oiq"][:k]), ("rx_sym", d["osym"][:k])):
+                rows = int(t.shape[0])
+                keep = max(1, per // (4 * (2 if t.dim() == 2 else 1)))
+                if rows > keep:
+                    idx = np.sort(np.random.default_rng(SEED).choice(rows, keep, replace=False))
+                    t = t[torch.from_numpy(idx).to(t.device)]
+                out.append((f"ch{c:02d}_{name}", t.to(torch.float32).cpu().numpy()))
+        return out
 
     def fused(self):
         """The form of the last step (modem_chain_fused): 1 one launch per channel whose RX
@@ -444,9 +496,13 @@ def run(args, runner_factory, dist=None, rank=0, world=1):
     # (tools/region_probe.py, profiles/r03_region_probe.txt); the driver's 20-step region
     # (~1.2 ms) otherwise measures where it falls in that transient, not the steady state the
     # metric is about. The timed region below is still exactly --steps full steps.
+    # The settling steps run on a twin of the runner (its buffers, handles of its own), so that
+    # the runner's own streams start at the warmup whatever the settling took (settle_twin).
+    settle_ms = getattr(args, "settle_ms", 0.0)
+    twin = r.settle_twin() if settle_ms > 0 and hasattr(r, "settle_twin") else None
     if dist is not None:
         dist.barrier()      # the ranks settle together and reach the timing barrier together
-    settle = settle_clocks(r, getattr(args, "settle_ms", 0.0))
+    settle = settle_clocks(twin if twin is not None else r, settle_ms)
     for _ in range(args.warmup):
         r.step()
     r.sync()
@@ -463,8 +519,54 @@ def run(args, runner_factory, dist=None, rank=0, world=1):
     dt = time.perf_counter() - t0
     if dist is not None:
         dt = dist.max_over_ranks(dt)
+    del twin
     total = nsamp * nch * args.steps * world
     value = total / dt / 1e6
+    # --dump-outputs: the arrays of the last timed step, before anything else runs on the buffers
+    dump = getattr(args, "dump_outputs", None)
+    if dump:
+        dump_outputs(dump, r.outputs(DUMP_BYTES // world), rank, world)
+    out = {
+        "metric": METRIC,
+        "value": round(value, 2),
+        "unit": "Msamples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "settle": settle,
+        "ms_per_step": round(dt / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "f16" if dtype == 1 else "f32",
+        "data": f"synthetic: splitmix64 bits (seed 0x5EED0000 + channel), one byte per bit, device-resident",
+        "config": {"workload": desc, "samples_per_gpu_per_step": nsamp * nch, "channels_per_gpu": nch,
+                   "channels_total": nch * world,
+                   "channels_per_launch": r.launch_channels() if hasattr(r, "launch_channels") else 1,
+                   "streams_per_gpu": len(getattr(r, "streams", [None])),
+                   "channel_batch": bool(getattr(r, "batch", False)),
+                   "ntaps": L, "sps": sps, "bits_per_symbol": bps, "rrc_beta": 0.35,
+                   "carrier": "Freq::new(1, 4) (fs/4)", "parallelism": f"{world} independent channel set(s), "
+                   "one per GPU, no collectives" + (f"; one job of {nch * world} channels, {nch} per GPU"
+                                                    if scaling == "strong" else "") + (f" (timing barrier and max over ranks: "
+                                                    f"{dist.td.get_backend()})" if dist is not None else "")},
+        "full": bool(getattr(args, "full", False)),
+    }
+    if args.amplitude != 1.0:
+        out["config"]["amplitude"] = args.amplitude
+    if dump:
+        out["dumped_outputs"] = dump
+    if out["full"]:
+        out.update(full_report(args, r, runner_factory, dist, rank, world, wl))
+    return out
+
+
+def full_report(args, r, runner_factory, dist, rank, world, wl):
+    """What --full adds to the line, measured after the timed steps in runs of their own: the
+    decisions checked against the symbols sent, the host gather of the decisions, the TX / RX /
+    chain legs by HIP events with their rooflines (and the two-launch chain beside a fused one),
+    C5 f32 as the out-of-cache roofline beside a C3 line, and the CPU oracle's rate."""
+    name, bps, L, sps, nsamp, nch, dtype, desc = wl
     ok = r.check()
     g_ms, g_bytes = r.gather_ms()
     if dist is not None:
@@ -507,28 +609,6 @@ def run(args, runner_factory, dist=None, rank=0, world=1):
         dom_traffic = None          # measured on another launch size (channel group)
     chain_gbs = b_moved / (t_chain * 1e-3) / 1e9
     out = {
-        "metric": METRIC,
-        "value": round(value, 2),
-        "unit": "Msamples/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "settle": settle,
-        "ms_per_step": round(dt / args.steps * 1e3, 4),
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "f16" if dtype == 1 else "f32",
-        "data": f"synthetic: splitmix64 bits (seed 0x5EED0000 + channel), one byte per bit, device-resident",
-        "config": {"workload": desc, "samples_per_gpu_per_step": nsamp * nch, "channels_per_gpu": nch,
-                   "channels_total": nch * world, "channels_per_launch": per_launch,
-                   "streams_per_gpu": len(getattr(r, "streams", [None])),
-                   "channel_batch": bool(getattr(r, "batch", False)),
-                   "ntaps": L, "sps": sps, "bits_per_symbol": bps, "rrc_beta": 0.35,
-                   "carrier": "Freq::new(1, 4) (fs/4)", "parallelism": f"{world} independent channel set(s), "
-                   "one per GPU, no collectives" + (f"; one job of {nch * world} channels, {nch} per GPU"
-                                                    if scaling == "strong" else "") + (f" (timing barrier and max over ranks: "
-                                                    f"{dist.td.get_backend()})" if dist is not None else "")},
         "roofline": {"bound": "hbm", "kernel": dom[0], "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": dom_traffic,
                      "algorithmic_bytes_per_launch": dom[2], "mean_launch_ms": round(dom[1], 5)},
@@ -551,14 +631,20 @@ def run(args, runner_factory, dist=None, rank=0, world=1):
                    "what": "D2H of every rank's u8 decisions (all channels) into pinned host memory, "
                            "HIP events on the launch stream, max over ranks; not in the timed region"},
     }
-    if args.amplitude != 1.0:
-        out["config"]["amplitude"] = args.amplitude
     if rank == 0 and world == 1 and args.config == "c3" and not args.no_out_of_cache:
-        del r
         out["roofline_out_of_cache"] = out_of_cache_roofline(runner_factory)
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(wl, args.cpu_samples)
     return out
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+    """--dump-outputs: every (name, array) pair as path/<name>.npy in float32 (a rank of a
+    multi-GPU run writes its own channels as rank<r>_<name>.npy)."""
+    os.makedirs(path, exist_ok=True)
+    pre = f"rank{rank}_" if world > 1 else ""
+    for name, a in arrays:
+        np.save(os.path.join(path, f"{pre}{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def settle_clocks(r, settle_ms):
@@ -656,6 +742,12 @@ def _parser():
     ap.add_argument("--amplitude", type=float, default=1.0)
     # skip the C5 f32 out-of-Infinity-Cache roofline measured after the C3 line
     ap.add_argument("--no-out-of-cache", action="store_true")
+    # everything beside the headline figure (full_report: the decisions check, the gather, the
+    # per-kernel legs and rooflines, the out-of-cache roofline, the CPU baseline); --cpu-samples,
+    # --no-cpu-baseline and --no-out-of-cache trim a --full run and mean nothing without it
+    ap.add_argument("--full", action="store_true")
+    # after the timed steps: the last step's arrays as DIR/<name>.npy (GpuRunner.outputs)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None)
     return ap
 
 

@@ -80,7 +80,7 @@ def _worker(rank, world, port, outdir, config="tiny"):
     bench.WORKLOADS["tinyjob"] = ("qam16", 4, 129, 4, 1 << 12, 4, 0, "tinyjob: 4 channels x 4096 samples")
     bench.FIXED_TOTAL.add("tinyjob")
     args = bench.argparse.Namespace(config=config, steps=3, warmup=1, no_cpu_baseline=True, cpu_samples=0,
-                                    amplitude=1.0, no_out_of_cache=True, settle_ms=0.0)
+                                    amplitude=1.0, no_out_of_cache=True, settle_ms=0.0, full=True)
     runners = []
 
     def factory(wl, r):
@@ -232,6 +232,50 @@ def test_settle_clocks_runs_untimed_steps_for_the_budget():
     assert out["steps"] == r.steps and r.steps >= 20
     assert 60.0 <= out["ms"] <= dt + 1.0 and dt < 60.0 + 20.0     # batches end near the budget
     assert r.syncs < r.steps                                      # steps are queued in batches
+
+
+def test_plain_run_times_the_steps_only(tmp_path):
+    """bench.run without --full: the settling (on the runner's twin), the warmup and exactly
+    --steps timed steps, the dump of the last step's arrays, and nothing after them (no check,
+    gather or kernel legs); the line keeps the headline fields. --full and --dump-outputs parse."""
+    import bench
+
+    class R:
+        def __init__(self, calls):
+            self.calls = calls
+            self.n = 0
+
+        def step(self):
+            self.n += 1
+            self.calls.append("step")
+
+        def sync(self):
+            pass
+
+        def settle_twin(self):
+            self.calls.append("twin")
+            return R([])
+
+        def outputs(self, budget):
+            assert budget == bench.DUMP_BYTES
+            return [("ch00_rx_sym", np.arange(5, dtype=np.uint8) + self.n)]
+
+        def __getattr__(self, name):
+            if name in ("check", "gather_ms", "kernel_times_ms", "two_launch_chain_ms", "fused"):
+                raise AssertionError(f"a plain run called {name}")
+            raise AttributeError(name)
+
+    a = bench._parser().parse_args(["--steps", "4", "--warmup", "2", "--settle-ms", "5", "--dump-outputs",
+                                    str(tmp_path / "d")])
+    assert a.full is False and bench._parser().parse_args(["--full"]).full is True
+    calls = []
+    out = bench.run(a, lambda wl, rank: R(calls))
+    assert calls == ["twin"] + ["step"] * 6
+    assert out["full"] is False and out["steps"] == 4 and out["ms_per_step"] >= 0 and out["settle"]["steps"] >= 1
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out
+    got = np.load(tmp_path / "d" / "ch00_rx_sym.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, np.arange(5) + 6)
 
 
 def test_spawn_ends_ranks_when_one_fails():

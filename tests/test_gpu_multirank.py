@@ -31,7 +31,7 @@ def _worker(rank, world, port, outdir):
     td.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
     bench.WORKLOADS["small"] = ("qam16", 4, 129, 4, 1 << 18, 2, 0, "small: 2 channels x 2^18 C3 samples")
     args = bench.argparse.Namespace(config="small", steps=20, warmup=3, no_cpu_baseline=True, cpu_samples=0,
-                                    amplitude=1.0, no_out_of_cache=True)
+                                    amplitude=1.0, no_out_of_cache=True, full=True)
     runner = []
 
     def factory(wl, r):
@@ -68,7 +68,7 @@ def test_bench_gpus_flag_two_ranks():
     sys.path.insert(0, ROOT)
     import bench
     out = bench.main(["--gpus", "2", "--config", "c4", "--steps", "10", "--warmup", "3", "--settle-ms", "50",
-                      "--no-cpu-baseline"])
+                      "--full", "--no-cpu-baseline"])
     assert out["n_gpus"] == 2 and out["scaling"] == "strong"
     assert out["config"]["channels_per_gpu"] == 32 and out["config"]["channels_total"] == 64
     assert out["config"]["channels_per_launch"] == 8
@@ -86,7 +86,7 @@ def test_c4_job_one_gpu_groups_of_four():
     sys.path.insert(0, ROOT)
     import bench
     out = bench.main(["--config", "c4", "--group", "4", "--steps", "5", "--warmup", "2", "--settle-ms", "20",
-                      "--no-cpu-baseline"])
+                      "--full", "--no-cpu-baseline"])
     assert out["n_gpus"] == 1 and out["scaling"] == "strong"
     assert out["config"]["channels_per_gpu"] == 64 and out["config"]["channels_per_launch"] == 4
     assert out["decisions_match_sent"] is True
@@ -103,7 +103,7 @@ def test_rccl_branch_under_launcher(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "1", "--config", "c2", "--steps", "20", "--warmup", "3", "--settle-ms", "0",
-           "--no-cpu-baseline", "--no-out-of-cache"]
+           "--full", "--no-cpu-baseline", "--no-out-of-cache"]
     r = subprocess.run(cmd, cwd=str(tmp_path), capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -12,7 +12,7 @@ cd ${GRAFT_REPO_ROOT:-.}
 export TMPDIR=/tmp
 o=gpurun_out/${OUT:-ab}; mkdir -p $o
 B=${BENCH:-"--steps 200 --warmup 50 --settle-ms 200"}
-B="$B --no-cpu-baseline --no-out-of-cache"
+B="$B --full --no-cpu-baseline --no-out-of-cache"
 line() { python3 -c "
 import json;d=json.loads([l for l in open('$1') if l.startswith('{')][-1]);c=d['chain_roofline']
 print('$2', d['value'], d['ms_per_step'], 'tx', c['tx_ms'], 'rx', c['rx_ms'], 'chain', c['chain_ms'], d['decisions_match_sent'])"; }
@@ -32,6 +32,6 @@ for rep in $(seq 1 ${REPS:-2}); do
   done
 done
 for i in $(seq 1 ${DRV:-0}); do
-  timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > $o/c3_drv$i.json 2> $o/c3_drv$i.err || { tail -3 $o/c3_drv$i.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --full > $o/c3_drv$i.json 2> $o/c3_drv$i.err || { tail -3 $o/c3_drv$i.err; exit 1; }
   line $o/c3_drv$i.json "c3 driver-style $i" | tee -a $o/lines.txt
 done

@@ -37,7 +37,7 @@ c4-rot)
   done; done
   OUT=${OUT:-probe}/ab VARIANTS="tree:MODEM_BATCH_ROT=0 tree" CONFIGS="c4" REPS=2 bash tools/ab_variants.sh ;;
 c4-groups)
-  B="--steps 100 --warmup 30 --settle-ms 200 --no-cpu-baseline --no-out-of-cache"
+  B="--steps 100 --warmup 30 --settle-ms 200 --full --no-cpu-baseline --no-out-of-cache"
   for rep in 1 2; do for v in "8:2" "4:2" "8:0" "2:2"; do
     g=${v%%:*}; nt=${v#*:}
     MODEM_TX_NT=$nt timeout -k 10 300 python3 bench.py --config c4 --group $g $B > $o/c4_g${g}_nt$nt.json 2> $o/err || { tail -3 $o/err; exit 1; }

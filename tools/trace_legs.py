@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The bench's three timing legs read back from a rocprofv3 kernel trace of the bench command
-(run_kernel_trace.csv): runs of back-to-back RX launches (the RX-only leg), of TX launches
+with --full (run_kernel_trace.csv): runs of back-to-back RX launches (the RX-only leg), of TX launches
 (TX-only) and of alternating TX, RX (the chain). For each run, span / launches (first start to
 last end, as the bench's two HIP events bracket it), median over runs — comparable with
 `chain_roofline.{tx_ms,rx_ms,chain_ms}` of the bench line. The per-dispatch averages of the
