@@ -58,7 +58,8 @@ extern "C" {
 /* 2: modem_tx_desc.q_offset; 3: the channel-batch entry points; 4: modem_rx_desc.phase_offset
  * (the descriptor grew 8 bytes: 80 -> 88), modem_pll_lock, MODEM_DTYPE_I16 and
  * MODEM_MIX_REFERENCE_REAL_EXACT; 5: modem_chain_* (no layout change; modem_chain_fused
- * added later, additive); 6: modem_chain_batch_* (additive, no layout change). Layouts:
+ * added later, additive); 6: modem_chain_batch_* (additive, no layout change; modem_demap_* and
+ * MODEM_DTYPE_I8 added later, additive: no descriptor, no layout change). Layouts:
  * INTEGRATION.md. */
 #define MODEM_HIP_ABI_VERSION 6
 
@@ -74,7 +75,9 @@ typedef enum {
 
 /* I16: real-valued samples, one native-endian int16 per sample (what `demodulate` reads from
  * stdin, bin/util.rs:3-37); RX input only, with MODEM_MIX_REFERENCE_REAL_EXACT. */
-typedef enum { MODEM_DTYPE_F32 = 0, MODEM_DTYPE_F16 = 1, MODEM_DTYPE_I16 = 2 } modem_dtype;
+/* I8: one signed byte per value; only as the soft demapper's output dtype (modem_demap_create),
+ * every other entry point rejects it. */
+typedef enum { MODEM_DTYPE_F32 = 0, MODEM_DTYPE_F16 = 1, MODEM_DTYPE_I16 = 2, MODEM_DTYPE_I8 = 3 } modem_dtype;
 
 /* TX output: complex (i,q)*e^{j phase} (IQSample::modulate, modulator.rs:45-48); the
  * un-mixed baseband (what `modulate --iq` writes, modulate.rs:110-113); or only the real
@@ -331,6 +334,36 @@ modem_status modem_fir_create(const float* taps, uint32_t ntaps, int device, mod
  * bit-identical: the reference's fold order, separate multiply and add. */
 modem_status modem_fir_process(modem_fir* h, const float* in, float* out, size_t n, void* stream);
 modem_status modem_fir_destroy(modem_fir* h);
+
+/* ---- Soft-decision demapper (GLUE: the reference has no soft output) --------------------- */
+/* Per-bit max-log LLRs of received points r = (re, im) — the decimated I/Q that modem_rx_process
+ * writes — against a constellation lut[s] = (lut[2s], lut[2s+1]), s = 0 .. 2^bps - 1:
+ *   d(s)           = (re - lut[2s])^2 + (im - lut[2s+1])^2     (the differences in f32, as the
+ *                                                                NEAREST slicer forms them)
+ *   llr[k*bps + j] = scale * (min_{s: bit_j(s)=1} d(s) - min_{s: bit_j(s)=0} d(s))
+ * where bit j of s is (s >> (bps-1-j)) & 1: j = 0 is the MSB, the order of bytes_to_bits
+ * (digital/util.rs:5-11) and of the TX's one-byte-per-bit input. A positive LLR means "bit 0 is
+ * more likely"; the hard bit is llr < 0. Pass scale = 1/N0 (times a quantiser gain if wanted).
+ * Output dtypes: F32; F16 (round to nearest, saturating to +-65504, never inf); I8
+ * (rint(clamp(llr, -127, 127))). Input: F32 or F16 I/Q (F16 widened exactly). NaN input:
+ * unspecified.
+ * Two device paths with the same results up to f32 rounding: when the table is, bitwise, a product
+ * grid with an even bit split (lut[2((a<<h)|b)] depends only on a, lut[2((a<<h)|b)+1] only on
+ * b, h = bps/2: every QAM at phase 0) MODEM_DEMAP_AUTO evaluates the 2^h levels per axis
+ * instead of the 2^bps points; MODEM_DEMAP_GENERAL forces the all-points path. */
+typedef struct modem_demap modem_demap;
+typedef enum { MODEM_DEMAP_AUTO = 0, MODEM_DEMAP_GENERAL = 1 } modem_demap_path_req;
+
+/* lut: 2 * 2^bps floats from modem_phasor_lut (host memory, copied). */
+modem_status modem_demap_create(const float* lut, uint32_t bits_per_symbol, int32_t in_dtype,
+                                int32_t out_dtype, int32_t path, int device, modem_demap** out);
+/* iq: nsym interleaved (i,q) of in_dtype; llr: nsym*bps values of out_dtype; cap in LLR values
+ * (cap < nsym*bps: CAPACITY, nothing written). The handle carries no stream state: cutting a
+ * buffer into several calls gives bit-identical output. scale must be finite. */
+modem_status modem_demap_process(modem_demap* h, const void* iq, size_t nsym, float scale,
+                                 void* llr, size_t cap, void* stream);
+int modem_demap_path(const modem_demap* h);   /* 1 = axis, 0 = general, -1 = NULL */
+modem_status modem_demap_destroy(modem_demap* h);
 
 /* ---- synthetic input (GLUE): splitmix64 bit stream, one byte per bit ------------------- */
 /* bit i = (word[i/64] >> (i%64)) & 1, word j = splitmix64 output j+1 from `seed`.

@@ -36,6 +36,7 @@ __all__ = [
     "rrc_taps", "DigitalModulator", "DemodulatorRx", "FIRFilter", "prng_bits",
     "MIX_COMPLEX", "MIX_REFERENCE_REAL", "MIX_REFERENCE_REAL_EXACT", "OUT_IQ_MIXED", "OUT_IQ_BASEBAND", "OUT_REAL",
     "TxBatchPlan", "RxBatchPlan", "SLICER_NONE", "SLICER_NEAREST", "SLICER_QAM_AXIS", "DTYPE_F32", "DTYPE_F16", "DTYPE_I16",
+    "SoftDemapper", "DTYPE_I8", "DEMAP_AUTO", "DEMAP_GENERAL",
 ]
 
 PI32 = float(np.float32(math.pi))      # std::f32::consts::PI
@@ -43,6 +44,8 @@ PI32 = float(np.float32(math.pi))      # std::f32::consts::PI
 MODEM_OK, ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_NO_DEVICE, ERR_CAPACITY, ERR_ALLOC = (
     0, -1, -2, -3, -4, -5, -6)
 DTYPE_F32, DTYPE_F16, DTYPE_I16 = 0, 1, 2   # I16: real samples, RX input (demodulate)
+DTYPE_I8 = 3                                # only as SoftDemapper's out_dtype
+DEMAP_AUTO, DEMAP_GENERAL = 0, 1
 OUT_IQ_MIXED, OUT_IQ_BASEBAND, OUT_REAL = 0, 1, 2
 MIX_COMPLEX, MIX_REFERENCE_REAL, MIX_REFERENCE_REAL_EXACT = 0, 1, 2
 SLICER_NONE, SLICER_NEAREST, SLICER_QAM_AXIS = 0, 1, 2
@@ -161,6 +164,10 @@ def load_library():
         "modem_fir_process": (st, [vp, vp, vp, sz, vp]),
         "modem_fir_destroy": (st, [vp]),
         "modem_prng_bits": (st, [u64, vp, sz, c.c_int, vp]),
+        "modem_demap_create": (st, [fp, u32, c.c_int32, c.c_int32, c.c_int32, c.c_int, c.POINTER(vp)]),
+        "modem_demap_process": (st, [vp, vp, sz, f32, vp, sz, vp]),
+        "modem_demap_path": (c.c_int, [vp]),
+        "modem_demap_destroy": (st, [vp]),
         "modem_chain_create": (st, [vp, vp, vp, sz, vp, sz, vp, vp, sz, c.POINTER(vp)]),
         "modem_chain_run": (st, [vp, c.POINTER(sz), c.POINTER(sz), vp]),
         "modem_chain_fused": (c.c_int, [vp]),
@@ -303,6 +310,10 @@ class _Phasor:
                                                   ctypes.byref(sd)), "slicer")
         return sd
 
+    def demapper(self, **kw) -> "SoftDemapper":
+        """SoftDemapper over this phasor's table (in_dtype, out_dtype, path, device)."""
+        return SoftDemapper(self, **kw)
+
 
 class BPSK(_Phasor):
     """bpsk.rs:4-32."""
@@ -394,6 +405,9 @@ class _SamplePhasor(_Phasor):
 
     def slicer(self):
         raise ModemError(ERR_UNSUPPORTED, f"{type(self).__name__}: no memoryless slicer")
+
+    def demapper(self, **kw):
+        raise ModemError(ERR_UNSUPPORTED, f"{type(self).__name__}: no memoryless demapper")
 
     def i(self, s, b):
         raise ModemError(ERR_UNSUPPORTED, "evaluated per sample inside DigitalModulator")
@@ -541,7 +555,8 @@ def _empty_like_input(ref, shape, np_dtype):
     """Allocate an output on the same side (device tensor / host ndarray) as `ref`."""
     if _is_torch(ref):
         import torch
-        tdt = {np.float32: torch.float32, np.float16: torch.float16, np.uint8: torch.uint8}[np_dtype]
+        tdt = {np.float32: torch.float32, np.float16: torch.float16, np.uint8: torch.uint8,
+               np.int8: torch.int8}[np_dtype]
         return torch.empty(shape, dtype=tdt, device=ref.device)
     return np.empty(shape, dtype=np_dtype)
 
@@ -901,6 +916,58 @@ class FIRFilter:
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.modem_fir_destroy(self._h)
+            self._h = None
+
+
+# ------------------------------------------------------------------ soft demapper ----
+_LLR_DTYPE = {DTYPE_F32: np.float32, DTYPE_F16: np.float16, DTYPE_I8: np.int8}
+
+
+class SoftDemapper:
+    """Per-bit max-log LLRs of received points (GLUE: the reference ends at hard symbols).
+
+    llr[k, j] = scale * (min_{s: bit_j(s)=1} |r_k - lut[s]|^2 - min_{s: bit_j(s)=0} |r_k - lut[s]|^2),
+    j = 0 the MSB (the order of the TX's one-byte-per-bit input); positive = "bit 0 more likely",
+    the hard bit is llr < 0. `phasor_or_lut`: a memoryless phasor or its (2^bps, 2) float32 table.
+    `process(iq, scale)` takes the (n, 2) I/Q that `DemodulatorRx.process` returns — a CUDA
+    tensor (asynchronous, on the current stream) or a numpy array — and returns (n, bps) of
+    out_dtype (float32, float16 saturating at +-65504, or int8 = rint(clamp(llr, -127, 127)))
+    on the same side. Pass scale = 1/N0, times a quantiser gain for int8."""
+
+    def __init__(self, phasor_or_lut, in_dtype: int = DTYPE_F32, out_dtype: int = DTYPE_F32,
+                 path: int = DEMAP_AUTO, device: int = 0):
+        lut = phasor_or_lut.lut() if isinstance(phasor_or_lut, _Phasor) else phasor_or_lut
+        self.lut = np.ascontiguousarray(lut, dtype=np.float32).reshape(-1, 2)
+        n = self.lut.shape[0]
+        bps = n.bit_length() - 1
+        if n < 2 or n != 1 << bps:
+            raise ModemPanic(ERR_INVALID_ARG, f"SoftDemapper: a table of {n} points is not 2^bps")
+        self.bps, self.in_dtype, self.out_dtype, self.device = bps, in_dtype, out_dtype, device
+        h = ctypes.c_void_p()
+        _check(load_library().modem_demap_create(_fptr(self.lut), bps, in_dtype, out_dtype, path, device,
+                                                 ctypes.byref(h)), "SoftDemapper")
+        self._h = h
+
+    @property
+    def path(self) -> str:
+        return "axis" if load_library().modem_demap_path(self._h) == 1 else "general"
+
+    def process(self, iq, scale: float, out=None, stream=None):
+        n = _check_rx_input(iq, self.in_dtype, "SoftDemapper.process")
+        llr = out if out is not None else _empty_like_input(iq, (n, self.bps), _LLR_DTYPE[self.out_dtype])
+        if _dtype_name(llr) != np.dtype(_LLR_DTYPE[self.out_dtype]).name:
+            raise ValueError(f"SoftDemapper.process: out must be {np.dtype(_LLR_DTYPE[self.out_dtype]).name} "
+                             f"(the handle's out_dtype), got {_dtype_name(llr)}")
+        cap = 1
+        for d in llr.shape:
+            cap *= int(d)
+        _check(load_library().modem_demap_process(self._h, _ptr(iq), n, float(scale), _ptr(llr), cap,
+                                                  _stream_handle(stream, self.device)), "SoftDemapper.process")
+        return llr
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.modem_demap_destroy(self._h)
             self._h = None
 
 

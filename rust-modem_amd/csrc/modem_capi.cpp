@@ -1490,6 +1490,119 @@ modem_status modem_fir_process(modem_fir* h, const float* in, float* out, size_t
 
 modem_status modem_fir_destroy(modem_fir* h) { delete h; return MODEM_OK; }
 
+// ------------------------------------------------------------------- soft demapper ----
+struct modem_demap {
+    int device = 0;
+    uint32_t bps = 0;
+    int32_t in_dtype = 0, out_dtype = 0;
+    bool axis = false;
+    float* d_tab = nullptr;   // general: the 2^bps (i, q) points; axis: the I levels, then the Q levels
+    Stage in_stage, out_stage;
+    ~modem_demap() {
+        DeviceGuard g(device);
+        if (d_tab) (void)hipFree(d_tab);
+    }
+};
+
+// The table is a product grid with an even bit split, bitwise: lut[2((a<<h)|b)] depends only on
+// a, lut[2((a<<h)|b)+1] only on b (h = bps/2). levels: its 2^h I values, then its 2^h Q values —
+// the table's own floats, so the axis path's inputs are the general path's.
+static bool demap_axis_levels(const float* lut, uint32_t bps, std::vector<float>* levels) {
+    if (bps % 2) return false;
+    const uint32_t h = bps / 2, n = 1u << h;
+    levels->resize(2 * n);
+    for (uint32_t a = 0; a < n; ++a) {
+        (*levels)[a] = lut[2 * (a << h)];
+        (*levels)[n + a] = lut[2 * a + 1];
+    }
+    for (uint32_t a = 0; a < n; ++a)
+        for (uint32_t b = 0; b < n; ++b) {
+            const float* pt = lut + 2 * ((a << h) | b);
+            if (std::memcmp(&pt[0], &(*levels)[a], sizeof(float)) != 0 ||
+                std::memcmp(&pt[1], &(*levels)[n + b], sizeof(float)) != 0) return false;
+        }
+    return true;
+}
+
+static size_t demap_out_bytes(int32_t dt) { return dt == MODEM_DTYPE_F32 ? 4 : dt == MODEM_DTYPE_F16 ? 2 : 1; }
+
+modem_status modem_demap_create(const float* lut, uint32_t bits_per_symbol, int32_t in_dtype, int32_t out_dtype,
+                                int32_t path, int device, modem_demap** out) {
+    if (!out) return MODEM_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (!lut || bits_per_symbol < 1 || bits_per_symbol > 8) return MODEM_ERR_INVALID_ARG;
+    if (in_dtype != MODEM_DTYPE_F32 && in_dtype != MODEM_DTYPE_F16) return MODEM_ERR_INVALID_ARG;
+    if (out_dtype != MODEM_DTYPE_F32 && out_dtype != MODEM_DTYPE_F16 && out_dtype != MODEM_DTYPE_I8)
+        return MODEM_ERR_INVALID_ARG;
+    if (path != MODEM_DEMAP_AUTO && path != MODEM_DEMAP_GENERAL) return MODEM_ERR_INVALID_ARG;
+    if (!device_ok(device)) return MODEM_ERR_NO_DEVICE;
+    DeviceGuard g(device);
+    if (!g.ok) return MODEM_ERR_NO_DEVICE;
+    modem_demap* h = new (std::nothrow) modem_demap;
+    if (!h) return MODEM_ERR_ALLOC;
+    h->device = device;
+    h->bps = bits_per_symbol;
+    h->in_dtype = in_dtype;
+    h->out_dtype = out_dtype;
+    std::vector<float> levels;
+    h->axis = path == MODEM_DEMAP_AUTO && demap_axis_levels(lut, bits_per_symbol, &levels);
+    const float* tab = h->axis ? levels.data() : lut;
+    const size_t ntab = h->axis ? levels.size() : (size_t)2 << bits_per_symbol;
+    modem_status st;
+    if ((st = dalloc(&h->d_tab, ntab))) { delete h; return st; }
+    if (hipMemcpy(h->d_tab, tab, ntab * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError(); delete h; return MODEM_ERR_HIP;
+    }
+    *out = h;
+    return MODEM_OK;
+}
+
+modem_status modem_demap_process(modem_demap* h, const void* iq, size_t nsym, float scale, void* llr, size_t cap,
+                                 void* stream) {
+    if (!h || !std::isfinite(scale) || (nsym && (!iq || !llr))) return MODEM_ERR_INVALID_ARG;
+    if (nsym > SIZE_MAX / 8) return MODEM_ERR_INVALID_ARG;
+    const size_t nllr = nsym * h->bps;
+    if (cap < nllr) return MODEM_ERR_CAPACITY;
+    if (nsym == 0) return MODEM_OK;
+    const PtrKind ki = ptr_kind(iq, h->device), ko = ptr_kind(llr, h->device);
+    if (ki == PTR_FOREIGN || ko == PTR_FOREIGN) return MODEM_ERR_INVALID_ARG;
+    const size_t in_bytes = nsym * (h->in_dtype == MODEM_DTYPE_F16 ? 4 : 8), ob = demap_out_bytes(h->out_dtype);
+    // device pointers must be element-aligned (the kernel picks its access widths from there up)
+    if ((ki == PTR_DEVICE && reinterpret_cast<uintptr_t>(iq) % (h->in_dtype == MODEM_DTYPE_F16 ? 2 : 4)) ||
+        (ko == PTR_DEVICE && reinterpret_cast<uintptr_t>(llr) % ob)) return MODEM_ERR_INVALID_ARG;
+    DeviceGuard g(h->device);
+    if (!g.ok) return MODEM_ERR_NO_DEVICE;
+    hipStream_t s = (hipStream_t)stream;
+    modem_status st;
+    const void* din = iq;
+    void* dout = llr;
+    if (ki == PTR_HOST) {
+        if ((st = h->in_stage.ensure(in_bytes))) return st;
+        HIP_TRY(hipMemcpyAsync(h->in_stage.p, iq, in_bytes, hipMemcpyHostToDevice, s));
+        din = h->in_stage.p;
+    }
+    const bool host_out = ko == PTR_HOST;
+    if (host_out) {
+        if ((st = h->out_stage.ensure(nllr * ob))) return st;
+        dout = h->out_stage.p;
+    }
+    mk::DemapParams p{};
+    p.iq = din;
+    p.llr = dout;
+    p.tab = h->d_tab;
+    p.nsym = (int64_t)nsym;
+    p.scale = scale;
+    p.bps = (int32_t)h->bps;
+    HIP_TRY(mk::launch_demap(p, h->axis, h->in_dtype, h->out_dtype, s));
+    if (host_out) HIP_TRY(hipMemcpyAsync(llr, dout, nllr * ob, hipMemcpyDeviceToHost, s));
+    if (host_out || din != iq) HIP_TRY(hipStreamSynchronize(s));
+    return MODEM_OK;
+}
+
+int modem_demap_path(const modem_demap* h) { return h ? (h->axis ? 1 : 0) : -1; }
+
+modem_status modem_demap_destroy(modem_demap* h) { delete h; return MODEM_OK; }
+
 modem_status modem_prng_bits(uint64_t seed, uint8_t* out, size_t nbits, int device, void* stream) {
     if (nbits && !out) return MODEM_ERR_INVALID_ARG;
     if (nbits && (!is_device_ptr(out) || foreign_ptr(out, device))) return MODEM_ERR_INVALID_ARG;

@@ -187,6 +187,19 @@ hipError_t rxm_sel(const RxParams& p, int decim, int nks, const void* tables, hi
 template <typename T>
 hipError_t rxm_sel_batch(const RxBatch& b, int decim, int nks, const void* tables, hipStream_t s);
 hipError_t launch_fir(const FirParams& p, hipStream_t s);
+// Soft demapper (modem_demap.hip): per-bit max-log LLRs of nsym received points, one lane per
+// symbol. General path: tab = the 2^bps (i, q) points. Axis path (a product grid with an even
+// bit split, checked by modem_demap_create): tab = the 2^(bps/2) I levels, then the Q levels.
+struct DemapParams {
+    const void* iq;          // nsym interleaved (i, q), f32 or f16
+    void* llr;               // nsym * bps values, symbol k's bps values contiguous, MSB first
+    const float* tab;        // device table (see above)
+    int64_t nsym;
+    float scale;
+    int32_t bps;
+};
+// out_dtype: 0 f32, 1 f16 (saturating), 3 i8 (rint of the value clamped to +-127)
+hipError_t launch_demap(const DemapParams& p, bool axis, int in_dtype, int out_dtype, hipStream_t s);
 hipError_t launch_phases(float w, uint64_t s0, size_t n, float* out, hipStream_t s);
 hipError_t launch_prng_bits(uint64_t seed, uint8_t* out, size_t nbits, hipStream_t s);
 
