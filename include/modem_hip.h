@@ -59,8 +59,8 @@ extern "C" {
  * (the descriptor grew 8 bytes: 80 -> 88), modem_pll_lock, MODEM_DTYPE_I16 and
  * MODEM_MIX_REFERENCE_REAL_EXACT; 5: modem_chain_* (no layout change; modem_chain_fused
  * added later, additive); 6: modem_chain_batch_* (additive, no layout change; modem_demap_* and
- * MODEM_DTYPE_I8 added later, additive: no descriptor, no layout change). Layouts:
- * INTEGRATION.md. */
+ * MODEM_DTYPE_I8 added later, additive: no descriptor, no layout change; modem_tx_scan_states
+ * and modem_tx_scan_path likewise). Layouts: INTEGRATION.md. */
 #define MODEM_HIP_ABI_VERSION 6
 
 typedef enum {
@@ -219,7 +219,8 @@ modem_status modem_tx_process(modem_tx* h, const uint8_t* bits, size_t nbits, vo
  * (sps, taps, bits per symbol, mixed I/Q output of one dtype, device) and every buffer is
  * device memory, up to 8 channels share one kernel launch. When every handle has the same
  * scanned phasor kind (DMPSK, MFSK, BFSK: a serial f32 state recurrence per stream,
- * dmpsk.rs:29-33, mfsk.rs:68-75, bfsk.rs:42-53) and every buffer is device memory, the
+ * dmpsk.rs:29-33, mfsk.rs:68-75, bfsk.rs:42-53) and every buffer is device memory (outs[c] may
+ * be NULL for a channel that completes no symbol), the
  * channels' state scans run as one launch, one lane per channel, each bit for bit its single
  * call's. Otherwise the calls run one by one.
  * No reference counterpart (the reference drives one DigitalModulator per stream,
@@ -231,6 +232,23 @@ modem_status modem_tx_process_batch(modem_tx* const* hs, size_t nch, const uint8
 modem_status modem_tx_flush(modem_tx* h, void* out, size_t cap, size_t* produced, void* stream);
 /* Samples that the next call will start at (Carrier.sample, carrier.rs:6). */
 uint64_t modem_tx_sample(const modem_tx* h);
+/* The per-symbol states that the serial scan of a DMPSK / MFSK / BFSK handle left on the device in
+ * its most recent modem_tx_process / modem_tx_process_batch call, copied to host memory `out`:
+ * one (x, y) pair of f32 per symbol that call produced (2 * *n floats), the state after the
+ * phasor's update() at that symbol's tick (dmpsk.rs:29-33, mfsk.rs:68-75, bfsk.rs:42-53):
+ *   DMPSK  x = phase          y = unspecified
+ *   MFSK   x = cur_coef       y = phase_offset
+ *   BFSK   x = phase          y = the previous bit (0.0 or 1.0)
+ * `cap` is in symbols. *n is the symbol count of that call: 0 before the first call and after a
+ * call that completed no symbol. cap < *n: MODEM_ERR_CAPACITY with *n set and `out` untouched. A
+ * handle whose phasor carries no scanned state: MODEM_ERR_UNSUPPORTED. Synchronises `stream` (pass
+ * the stream of that call) before it returns. For tests and diagnostics: it exposes the f32
+ * recurrence whose values the samples only show through sin / cos. */
+modem_status modem_tx_scan_states(const modem_tx* h, float* out, size_t cap, size_t* n, void* stream);
+/* How that call computed them: 1 = the handle's own scan launch (modem_tx_process, or a batch that
+ * ran its calls one by one), 2 = the bank launch of modem_tx_process_batch (one lane per channel),
+ * 0 = no such call yet or not a scanned phasor, -1 = h == NULL. The states are the same either way. */
+int modem_tx_scan_path(const modem_tx* h);
 modem_status modem_tx_destroy(modem_tx* h);
 
 /* ---- RX: Demodulator + matched filter + decimation + slicer ----------------------------- */

@@ -152,6 +152,8 @@ def load_library():
         "modem_tx_process_batch": (st, [c.POINTER(vp), sz, c.POINTER(vp), c.POINTER(sz), c.POINTER(vp),
                                         c.POINTER(sz), c.POINTER(sz), vp]),
         "modem_tx_sample": (u64, [vp]),
+        "modem_tx_scan_states": (st, [vp, fp, sz, c.POINTER(sz), vp]),
+        "modem_tx_scan_path": (c.c_int, [vp]),
         "modem_tx_destroy": (st, [vp]),
         "modem_rx_create": (st, [c.POINTER(_RxDesc), c.c_int, c.POINTER(vp)]),
         "modem_rx_process": (st, [vp, vp, sz, vp, vp, sz, c.POINTER(sz), vp]),
@@ -668,6 +670,28 @@ class DigitalModulator:
                                              _stream_handle(stream, self.device)), "DigitalModulator.flush")
         self.carrier.sample = int(load_library().modem_tx_sample(self._h))
         return out[: prod.value]
+
+    def scan_states(self, stream=None) -> np.ndarray:
+        """The (n, 2) float32 per-symbol states that the last process / process_batch call's serial
+        scan left on the device (modem_tx_scan_states; DMPSK: (phase, -), MFSK: (cur_coef,
+        phase_offset), BFSK: (phase, previous bit)); n = 0 before the first call and after a call
+        without a complete symbol. ModemError(ERR_UNSUPPORTED) for every other phasor."""
+        L = load_library()
+        sh = _stream_handle(stream, self.device)
+        n = ctypes.c_size_t()
+        status = L.modem_tx_scan_states(self._h, None, 0, ctypes.byref(n), sh)
+        if status != ERR_CAPACITY:
+            _check(status, "DigitalModulator.scan_states")
+        out = np.zeros((n.value, 2), np.float32)
+        if n.value:
+            _check(L.modem_tx_scan_states(self._h, _fptr(out), n.value, ctypes.byref(n), sh),
+                   "DigitalModulator.scan_states")
+        return out
+
+    def scan_path(self) -> str:
+        """How the last call computed those states (modem_tx_scan_path): "single" (this handle's
+        own scan launch), "bank" (process_batch's one launch, a lane per channel) or "none"."""
+        return {1: "single", 2: "bank"}.get(load_library().modem_tx_scan_path(self._h), "none")
 
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:

@@ -348,6 +348,8 @@ struct modem_tx {
     float ph_amp = 0.f, ph_freq = 0.f, ph_shift = 0.f, ph_max = 0.f;
     int ph_spb = 0, ph_map = 0;
     Stage scan_stage;               // per-symbol states of the scanned phasors
+    size_t scan_n = 0;              // symbols of the last call, in scan_stage (modem_tx_scan_states)
+    int scan_path = 0;              // how the last call scanned them (modem_tx_scan_path)
     Stage batch_params;             // a scan batch's parameter blocks, when this is its first handle
     float2* d_hist[2] = {nullptr, nullptr};
     uint8_t* d_carry[2] = {nullptr, nullptr};
@@ -644,6 +646,7 @@ static modem_status tx_launch(modem_tx* h, const uint8_t* dbits, size_t nbits, b
     tx_fill(h, dbits, nbits, flush, dout, nsym, ncarry_new, nsamp, p);
     p.scan = nullptr;
     if (phasor_scanned(h->ph_kind)) {
+        h->scan_n = 0;                  // the stage is rewritten (or regrown): no states until this call is queued
         if ((st = h->scan_stage.ensure((size_t)std::max<int64_t>(nsym, 1) * sizeof(float2)))) return st;
         p.scan = static_cast<float2*>(h->scan_stage.p);
     }
@@ -654,6 +657,7 @@ static modem_status tx_launch(modem_tx* h, const uint8_t* dbits, size_t nbits, b
     else
         HIP_TRY(mk::launch_tx(p, (int)h->sps, h->dtype, h->out_mode, s));
     tx_advance(h, flush, nsym, ncarry_new, nsamp);
+    if (p.scan) { h->scan_n = (size_t)nsym; h->scan_path = 1; }
     return MODEM_OK;
 }
 
@@ -726,6 +730,7 @@ static modem_status tx_scan_batch_run(modem_tx* const* hs, size_t nch, const uin
     std::vector<mk::TxParams> ps(nch);
     for (size_t c = 0; c < nch; ++c) {
         modem_tx* h = hs[c];
+        h->scan_n = 0;
         if ((st = h->scan_stage.ensure((size_t)std::max<int64_t>(nsym[c], 1) * sizeof(float2)))) return st;
         tx_fill(h, bits[c], nbits[c], false, outs[c], nsym[c], ncarry_new[c], (size_t)nsym[c] * h->sps, ps[c]);
         ps[c].scan = static_cast<float2*>(h->scan_stage.p);
@@ -739,6 +744,8 @@ static modem_status tx_scan_batch_run(modem_tx* const* hs, size_t nch, const uin
         modem_tx* h = hs[c];
         HIP_TRY(mk::launch_tx_phasor(ps[c], h->dtype, h->out_mode, s, true));
         tx_advance(h, false, nsym[c], ncarry_new[c], (size_t)nsym[c] * h->sps);
+        h->scan_n = (size_t)nsym[c];
+        h->scan_path = 2;
         produced[c] = (size_t)nsym[c] * h->sps;
     }
     return MODEM_OK;
@@ -761,8 +768,11 @@ modem_status modem_tx_process_batch(modem_tx* const* hs, size_t nch, const uint8
     bool scan = nch >= 2 && hs[0] != nullptr && phasor_scanned(hs[0]->ph_kind);
     for (size_t c = 0; scan && c < nch; ++c) {
         const modem_tx* h = hs[c];
+        // (a channel that completes no symbol writes no sample: its `out` may be NULL, as in tx_run)
+        const bool writes = h && ((uint64_t)h->ncarry + nbits[c]) / h->bps > 0;
         scan = h && h->device == hs[0]->device && h->ph_kind == hs[0]->ph_kind &&
-               (nbits[c] == 0 || (bits[c] && is_device_ptr(bits[c]))) && outs[c] && is_device_ptr(outs[c]);
+               (nbits[c] == 0 || (bits[c] && is_device_ptr(bits[c]))) &&
+               (writes ? outs[c] && is_device_ptr(outs[c]) : !outs[c] || is_device_ptr(outs[c]));
         for (size_t e = 0; scan && e < c; ++e) scan = hs[e] != h;      // a handle at most once
     }
     if (scan) {
@@ -827,6 +837,22 @@ modem_status modem_tx_process_batch(modem_tx* const* hs, size_t nch, const uint8
     return MODEM_OK;
 }
 uint64_t modem_tx_sample(const modem_tx* h) { return h ? h->sample : 0; }
+modem_status modem_tx_scan_states(const modem_tx* h, float* out, size_t cap, size_t* n, void* stream) {
+    if (!h || !n) return MODEM_ERR_INVALID_ARG;
+    *n = 0;
+    if (!phasor_scanned(h->ph_kind)) return MODEM_ERR_UNSUPPORTED;
+    *n = h->scan_n;
+    if (cap < h->scan_n) return MODEM_ERR_CAPACITY;
+    if (h->scan_n && !out) return MODEM_ERR_INVALID_ARG;
+    DeviceGuard g(h->device);
+    if (!g.ok) return MODEM_ERR_NO_DEVICE;
+    const hipStream_t s = (hipStream_t)stream;
+    if (h->scan_n)
+        HIP_TRY(hipMemcpyAsync(out, h->scan_stage.p, h->scan_n * sizeof(float2), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return MODEM_OK;
+}
+int modem_tx_scan_path(const modem_tx* h) { return h ? h->scan_path : -1; }
 modem_status modem_tx_destroy(modem_tx* h) { delete h; return MODEM_OK; }
 
 // ------------------------------------------------------------------------------ RX ----

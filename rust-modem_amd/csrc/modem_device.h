@@ -3,6 +3,7 @@
 // helpers, sample I/O and the persistent-grid sizing used by every launcher.
 #pragma once
 #include "modem_internal.h"
+#include "modem_scan_step.h"
 
 #include <hip/hip_fp16.h>
 
@@ -21,8 +22,7 @@ namespace mk {
 // every non-negative finite f32 (checked exhaustively on the host: tests/test_phase_math.py),
 // so the phase is bit-identical. contract(off) keeps TWO_PI*f and the subtraction
 // separately rounded, as rustc does.
-constexpr float kTwoPi = 0x1.921fb6p+2f;   // std::f32::consts::PI * 2.0 (0x40c90fdb)
-constexpr float kRcp2Pi = 0x1.45f306p-3f;  // fl(1 / kTwoPi)
+// kTwoPi (std::f32::consts::PI * 2.0) and kRcp2Pi (fl(1 / kTwoPi)): modem_scan_step.h.
 
 __device__ __forceinline__ float phase_from_f(float w, float nf) {
 #pragma clang fp contract(off)

@@ -7,8 +7,11 @@ post-increment carrier sample to the phasor).
 
 DCQPSK's values come from a host table built with the reference's f32 formulas: bit-exact.
 The others take sin/cos of a per-sample argument: the f32 sample tolerance. The scanned
-phases must follow the reference's f32 rounding exactly — long streams (20 000 symbols, where
-a phase that drifted by an ulp per step would be off by far more than the tolerance) check it.
+phases must follow the reference's f32 rounding exactly, and these samples do not check that:
+a state that is off by 2 pi, or by a few ulp after the next reduction (a floor off by one in
+the device's division-free mod_trig), has the same sine and cosine within the tolerance, however
+long the stream. tests/test_gpu_scan_states.py reads the states themselves back and compares
+them with the oracle's bit for bit (tests/test_scan_states.py: the same on the CPU).
 """
 import ctypes
 
@@ -132,8 +135,11 @@ def test_scanned_batch_equals_single_calls(m, o, torch_cuda, name):
     bit for bit, over two calls (the handles' carried states resume) with ragged lengths (leftover
     bits, an empty channel) and different carrier offsets; the first call's samples are also within
     the f32 tolerance of the oracle for two channels. DMPSK runs the 64-channel bank of the
-    VERDICT r05 item 7 (dmpsk.rs:29-33), the other kinds 9 channels (two waves' worth of lanes
-    is the same code)."""
+    VERDICT r05 item 7 (dmpsk.rs:29-33: four workgroups of kScanCpw = 16 lanes), the other kinds
+    9 channels (one workgroup, 9 of its 16 lanes; a partial last workgroup after full ones and
+    parameters mixed within a kind: tests/test_gpu_scan_states.py, which also asserts that the
+    bank launch ran: the empty channel's output tensor has no address, and the batch takes a
+    NULL output for a channel without a complete symbol)."""
     torch = torch_cuda
     mk, ok, bps = SCANNED[name]
     nch = 64 if name == "dqpsk" else 9
