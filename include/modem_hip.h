@@ -60,7 +60,8 @@ extern "C" {
  * MODEM_MIX_REFERENCE_REAL_EXACT; 5: modem_chain_* (no layout change; modem_chain_fused
  * added later, additive); 6: modem_chain_batch_* (additive, no layout change; modem_demap_* and
  * MODEM_DTYPE_I8 added later, additive: no descriptor, no layout change; modem_tx_scan_states
- * and modem_tx_scan_path likewise). Layouts: INTEGRATION.md. */
+ * and modem_tx_scan_path likewise; modem_phasor_diff_lut, modem_phasor_tones, modem_diff_* and
+ * modem_fsk_* likewise). Layouts: INTEGRATION.md. */
 #define MODEM_HIP_ABI_VERSION 6
 
 typedef enum {
@@ -75,8 +76,8 @@ typedef enum {
 
 /* I16: real-valued samples, one native-endian int16 per sample (what `demodulate` reads from
  * stdin, bin/util.rs:3-37); RX input only, with MODEM_MIX_REFERENCE_REAL_EXACT. */
-/* I8: one signed byte per value; only as the soft demapper's output dtype (modem_demap_create),
- * every other entry point rejects it. */
+/* I8: one signed byte per value; only as an LLR output dtype (modem_demap_create,
+ * modem_diff_create, modem_fsk_create), every other entry point rejects it. */
 typedef enum { MODEM_DTYPE_F32 = 0, MODEM_DTYPE_F16 = 1, MODEM_DTYPE_I16 = 2, MODEM_DTYPE_I8 = 3 } modem_dtype;
 
 /* TX output: complex (i,q)*e^{j phase} (IQSample::modulate, modulator.rs:45-48); the
@@ -382,6 +383,76 @@ modem_status modem_demap_process(modem_demap* h, const void* iq, size_t nsym, fl
                                  void* llr, size_t cap, void* stream);
 int modem_demap_path(const modem_demap* h);   /* 1 = axis, 0 = general, -1 = NULL */
 modem_status modem_demap_destroy(modem_demap* h);
+
+/* ---- Noncoherent detectors (GLUE: the reference's Demodulator ends at filtered I/Q) ------- */
+/* Receivers for the phasors that carry state from symbol to symbol, which have no (I,Q) table and
+ * so neither a slicer nor a demapper: DMPSK (the information is in phase differences) and MFSK /
+ * BFSK (in tone energies). Neither needs a carrier-phase lock. Both produce, per symbol, a metric
+ * c(s) for every symbol value s and from it
+ *   sym[k]         = argmax_s c(s), lowest index on ties
+ *   llr[k*bps + j] = scale * (max_{s: bit_j(s)=0} c(s) - max_{s: bit_j(s)=1} c(s))
+ * with the demapper's bit order (bit j of s is (s >> (bps-1-j)) & 1, j = 0 the MSB), sign (a
+ * positive LLR means "bit 0 is more likely"; the hard bit is llr < 0), LLR dtypes (F32; F16
+ * saturating to +-65504; I8 = rint(clamp(llr, -127, 127))) and input dtypes (F32, or F16 widened
+ * exactly). scale must be finite. out_sym and llr may each be NULL. NaN input: unspecified. */
+
+/* Table of the differential detector for a DMPSK phasor (dmpsk.rs:29-33: the phase advances by
+ * `s as f32 * shift` at every symbol): lut[2s], lut[2s+1] = cos(a_s), sin(a_s), a_s the f32
+ * product (float)s * d->shift of dmpsk.rs:32, widened to double; cos and sin evaluated in double
+ * and rounded to f32. 2 * 2^bps floats. Any other phasor kind: MODEM_ERR_UNSUPPORTED. */
+modem_status modem_phasor_diff_lut(const modem_phasor_desc* d, float* lut);
+/* Tone frequencies of an MFSK or BFSK phasor in radians per sample, 2^bps floats:
+ *   omega[m] = carrier_sample_freq + coef(m) * d->freq      (in double from the f32 inputs,
+ *                                                            rounded to f32)
+ *   MFSK DefaultMap   coef(m) = 2m - (2^bps - 1)   mfsk.rs:23-27
+ *   MFSK IncreaseMap  coef(m) = 2m                 mfsk.rs:31-35
+ *   BFSK              coef(m) = m, bps = 1         bfsk.rs:27-29
+ * Pass the carrier's Freq::sample_freq() for MODEM_OUT_IQ_MIXED streams (the phasor's tone rides
+ * on the carrier, modulator.rs:45-48) and 0 for MODEM_OUT_IQ_BASEBAND streams. Any other phasor
+ * kind: MODEM_ERR_UNSUPPORTED. */
+modem_status modem_phasor_tones(const modem_phasor_desc* d, float carrier_sample_freq, float* omega);
+
+/* Differential detector, at symbol rate on the decimated I/Q that modem_rx_process writes
+ * (receives DMPSK, dmpsk.rs:29-43). For the received points r[k]:
+ *   z[k] = r[k] * conj(r[k-1])                    (f32)
+ *   c(s) = z.re * lut[2s] + z.im * lut[2s+1]
+ * r[-1] is the last point of the previous call; for the first call it is prev0 (host memory, two
+ * floats; NULL = (1, 0)). For a DMPSK transmitter prev0 = amplitude * (cos phase, sin phase): its
+ * first symbol is already a step away from the initial phase (modulator.rs:91-93). The handle
+ * carries that one point: cutting a buffer into several calls, calls with nsym == 0 included,
+ * gives bit-identical output. lut: 2 * 2^bps floats (host memory, copied), from
+ * modem_phasor_diff_lut or by hand. */
+typedef struct modem_diff modem_diff;
+modem_status modem_diff_create(const float* lut, uint32_t bits_per_symbol, const float prev0[2],
+                               int32_t in_dtype, int32_t llr_dtype, int device, modem_diff** out);
+/* iq: nsym interleaved (i,q) of in_dtype; out_sym: nsym bytes; llr: nsym*bps values of llr_dtype;
+ * cap in symbols (cap < nsym: CAPACITY, nothing written, the state unchanged). */
+modem_status modem_diff_process(modem_diff* h, const void* iq, size_t nsym, float scale,
+                                uint8_t* out_sym, void* llr, size_t cap, void* stream);
+modem_status modem_diff_destroy(modem_diff* h);
+
+/* Tone-bank energy detector, at sample rate directly on the complex samples that modem_tx_process
+ * writes (receives MFSK, mfsk.rs:60-75, and BFSK, bfsk.rs:23-55). Symbol k covers the stream
+ * samples k*sps .. k*sps + sps-1, counted from the handle's first input sample — the samples the
+ * modulator emits while symbol k is current (modulator.rs:85-100):
+ *   S[k,m] = sum_{i<sps} x[k*sps+i] * e^{-j*omega[m]*i}        (f32 accumulation, i ascending)
+ *   c(m)   = E[k,m] = S.re^2 + S.im^2
+ *   energy[k*2^bps + m] = E[k,m]                                (f32, may be NULL)
+ * The phase index i is relative to the symbol: a constant phase drops out of |S|^2, so the detector
+ * needs no carrier sample counter, and the phasor's f32 `s as f32` (mfsk.rs:61) does not enter.
+ * omega: 2^bps finite floats (host memory), from modem_phasor_tones or by hand; the twiddles are
+ * tabulated at create time (cos and sin of the double product omega[m] * i, rounded to f32).
+ * samples_per_symbol * 2^bps > 65536 (a 512 KiB table): MODEM_ERR_UNSUPPORTED.
+ * Streaming: the handle carries the < sps samples after the last whole symbol;
+ * *produced = floor((carried + n) / sps); cuts at any sample positions, n == 0 included, give
+ * output bit-identical to one call. cap in symbols (*produced > cap: CAPACITY, nothing written,
+ * the state unchanged). */
+typedef struct modem_fsk modem_fsk;
+modem_status modem_fsk_create(const float* omega, uint32_t bits_per_symbol, uint32_t samples_per_symbol,
+                              int32_t in_dtype, int32_t llr_dtype, int device, modem_fsk** out);
+modem_status modem_fsk_process(modem_fsk* h, const void* in, size_t n, float scale, uint8_t* out_sym,
+                               void* llr, float* energy, size_t cap, size_t* produced, void* stream);
+modem_status modem_fsk_destroy(modem_fsk* h);
 
 /* ---- synthetic input (GLUE): splitmix64 bit stream, one byte per bit ------------------- */
 /* bit i = (word[i/64] >> (i%64)) & 1, word j = splitmix64 output j+1 from `seed`.

@@ -37,6 +37,7 @@ __all__ = [
     "MIX_COMPLEX", "MIX_REFERENCE_REAL", "MIX_REFERENCE_REAL_EXACT", "OUT_IQ_MIXED", "OUT_IQ_BASEBAND", "OUT_REAL",
     "TxBatchPlan", "RxBatchPlan", "SLICER_NONE", "SLICER_NEAREST", "SLICER_QAM_AXIS", "DTYPE_F32", "DTYPE_F16", "DTYPE_I16",
     "SoftDemapper", "DTYPE_I8", "DEMAP_AUTO", "DEMAP_GENERAL",
+    "DiffDetector", "ToneDetector",
 ]
 
 PI32 = float(np.float32(math.pi))      # std::f32::consts::PI
@@ -170,6 +171,14 @@ def load_library():
         "modem_demap_process": (st, [vp, vp, sz, f32, vp, sz, vp]),
         "modem_demap_path": (c.c_int, [vp]),
         "modem_demap_destroy": (st, [vp]),
+        "modem_phasor_diff_lut": (st, [c.POINTER(_PhasorDesc), fp]),
+        "modem_phasor_tones": (st, [c.POINTER(_PhasorDesc), f32, fp]),
+        "modem_diff_create": (st, [fp, u32, fp, c.c_int32, c.c_int32, c.c_int, c.POINTER(vp)]),
+        "modem_diff_process": (st, [vp, vp, sz, f32, vp, vp, sz, vp]),
+        "modem_diff_destroy": (st, [vp]),
+        "modem_fsk_create": (st, [fp, u32, u32, c.c_int32, c.c_int32, c.c_int, c.POINTER(vp)]),
+        "modem_fsk_process": (st, [vp, vp, sz, f32, vp, vp, vp, sz, c.POINTER(sz), vp]),
+        "modem_fsk_destroy": (st, [vp]),
         "modem_chain_create": (st, [vp, vp, vp, sz, vp, sz, vp, vp, sz, c.POINTER(vp)]),
         "modem_chain_run": (st, [vp, c.POINTER(sz), c.POINTER(sz), vp]),
         "modem_chain_fused": (c.c_int, [vp]),
@@ -315,6 +324,11 @@ class _Phasor:
     def demapper(self, **kw) -> "SoftDemapper":
         """SoftDemapper over this phasor's table (in_dtype, out_dtype, path, device)."""
         return SoftDemapper(self, **kw)
+
+    def detector(self, *args, **kw):
+        """The noncoherent detector of a phasor that carries state from symbol to symbol (DMPSK,
+        MFSK, BFSK); every other phasor is received through slicer() / demapper()."""
+        raise ModemError(ERR_UNSUPPORTED, f"{type(self).__name__}: no noncoherent detector")
 
 
 class BPSK(_Phasor):
@@ -469,6 +483,37 @@ class DMPSK(_SamplePhasor):
         d.shift = self._shift
         return d
 
+    def diff_lut(self) -> np.ndarray:
+        """(2^bps, 2) float32: row s = (cos, sin) of the f32 step `s as f32 * shift` (dmpsk.rs:32),
+        the table of DiffDetector (modem_phasor_diff_lut)."""
+        out = np.zeros((1 << self.bits_per_symbol(), 2), dtype=np.float32)
+        _check(load_library().modem_phasor_diff_lut(ctypes.byref(self._desc()), _fptr(out)), "DMPSK.diff_lut")
+        return out
+
+    def detector(self, **kw) -> "DiffDetector":
+        """DiffDetector for this phasor (prev0, in_dtype, llr_dtype, device); prev0 defaults to the
+        point of the initial phase, amplitude * (cos phase, sin phase)."""
+        return DiffDetector(self, **kw)
+
+
+def _tones(self, carrier=None) -> np.ndarray:
+    """(2^bps,) float32 tone frequencies in radians per sample (modem_phasor_tones): the carrier's
+    sample frequency (a Carrier, a Freq or a float; None = 0, a baseband stream) plus the phasor's
+    coef(m) * deviation (mfsk.rs:23-35, bfsk.rs:27-29)."""
+    if isinstance(carrier, Freq):
+        w = carrier.sample_freq()
+    else:
+        w = 0.0 if carrier is None else float(getattr(carrier, "sample_freq", carrier))
+    out = np.zeros(1 << self.bits_per_symbol(), dtype=np.float32)
+    _check(load_library().modem_phasor_tones(ctypes.byref(self._desc()), w, _fptr(out)),
+           f"{type(self).__name__}.tones")
+    return out
+
+
+def _tone_detector(self, sps: int, carrier=None, **kw) -> "ToneDetector":
+    """ToneDetector over this phasor's tones on `carrier` (in_dtype, llr_dtype, device)."""
+    return ToneDetector(self, sps, carrier, **kw)
+
 
 class MFSK(_SamplePhasor):
     """mfsk.rs:37-85: MFSK::new(bits_per_symbol, deviation: Freq, amplitude, map);
@@ -484,6 +529,9 @@ class MFSK(_SamplePhasor):
         d.freq, d.mfsk_map = self._freq, self._map
         return d
 
+    tones = _tones
+    detector = _tone_detector
+
 
 class BFSK(_SamplePhasor):
     """bfsk.rs:4-56: BFSK::new(deviation: Freq, amplitude)."""
@@ -496,6 +544,9 @@ class BFSK(_SamplePhasor):
         d = super()._desc()
         d.freq = self._freq
         return d
+
+    tones = _tones
+    detector = _tone_detector
 
 
 def rrc_taps(ntaps: int, sps: int, beta: float = 0.35) -> np.ndarray:
@@ -992,6 +1043,132 @@ class SoftDemapper:
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.modem_demap_destroy(self._h)
+            self._h = None
+
+
+# ----------------------------------------------------------- noncoherent detectors ----
+def _check_out(x, np_dtype, what: str):
+    if _dtype_name(x) != np.dtype(np_dtype).name:
+        raise ValueError(f"{what} must be {np.dtype(np_dtype).name}, got {_dtype_name(x)}")
+    n = 1
+    for d in x.shape:
+        n *= int(d)
+    return n
+
+
+class DiffDetector:
+    """Differential detector (GLUE: the reference has none) for DMPSK (dmpsk.rs:29-43), at symbol
+    rate on the (n, 2) I/Q that `DemodulatorRx.process` returns.
+
+    z[k] = r[k] * conj(r[k-1]), c(s) = z.re * lut[s, 0] + z.im * lut[s, 1]; sym[k] = argmax_s c(s)
+    (lowest index on ties); llr[k, j] = scale * (max_{bit_j(s)=0} c(s) - max_{bit_j(s)=1} c(s)),
+    j = 0 the MSB, positive = "bit 0 more likely". r[-1] is the last point of the previous call,
+    `prev0` before the first. `phasor_or_table`: a DMPSK phasor or a (2^bps, 2) float32 table.
+    `process(iq, scale)` returns (sym, llr): (n,) uint8 and (n, bps) of llr_dtype, on the side of
+    the input (CUDA tensors, asynchronous on the current stream, or numpy arrays)."""
+
+    def __init__(self, phasor_or_table, prev0=None, in_dtype: int = DTYPE_F32, llr_dtype: int = DTYPE_F32,
+                 device: int = 0):
+        if isinstance(phasor_or_table, _Phasor):
+            ph = phasor_or_table
+            if not isinstance(ph, DMPSK):
+                raise ModemError(ERR_UNSUPPORTED, f"{type(ph).__name__}: no differential detector")
+            lut = ph.diff_lut()
+            if prev0 is None:
+                prev0 = (ph.amplitude * math.cos(ph._phase), ph.amplitude * math.sin(ph._phase))
+        else:
+            lut = phasor_or_table
+        self.lut = np.ascontiguousarray(lut, dtype=np.float32).reshape(-1, 2)
+        n = self.lut.shape[0]
+        bps = n.bit_length() - 1
+        if n < 2 or n != 1 << bps:
+            raise ModemPanic(ERR_INVALID_ARG, f"DiffDetector: a table of {n} rows is not 2^bps")
+        self.bps, self.in_dtype, self.llr_dtype, self.device = bps, in_dtype, llr_dtype, device
+        self.prev0 = None if prev0 is None else np.ascontiguousarray(prev0, dtype=np.float32).reshape(2)
+        h = ctypes.c_void_p()
+        _check(load_library().modem_diff_create(_fptr(self.lut), bps, None if self.prev0 is None else _fptr(self.prev0),
+                                                in_dtype, llr_dtype, device, ctypes.byref(h)), "DiffDetector")
+        self._h = h
+
+    def process(self, iq, scale: float = 1.0, out_sym=None, out_llr=None, stream=None):
+        n = _check_rx_input(iq, self.in_dtype, "DiffDetector.process")
+        sym = out_sym if out_sym is not None else _empty_like_input(iq, (n,), np.uint8)
+        llr = out_llr if out_llr is not None else _empty_like_input(iq, (n, self.bps), _LLR_DTYPE[self.llr_dtype])
+        cap = min(_check_out(sym, np.uint8, "DiffDetector.process: out_sym"),
+                  _check_out(llr, _LLR_DTYPE[self.llr_dtype], "DiffDetector.process: out_llr") // self.bps)
+        _check(load_library().modem_diff_process(self._h, _ptr(iq), n, float(scale), _ptr(sym), _ptr(llr), cap,
+                                                 _stream_handle(stream, self.device)), "DiffDetector.process")
+        return sym, llr
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.modem_diff_destroy(self._h)
+            self._h = None
+
+
+class ToneDetector:
+    """Tone-bank energy detector (GLUE: the reference has none) for MFSK (mfsk.rs:60-75) and BFSK
+    (bfsk.rs:23-55), at sample rate directly on the (n, 2) complex samples of `DigitalModulator`.
+
+    Symbol k covers the samples k*sps .. k*sps+sps-1 from the detector's first input sample:
+    E[k, m] = |sum_i x[k*sps+i] * e^{-j omega[m] i}|^2; sym[k] = argmax_m E[k, m] (lowest index on
+    ties); llr[k, j] = scale * (max_{bit_j(m)=0} E - max_{bit_j(m)=1} E), j = 0 the MSB.
+    `omega_or_phasor`: an MFSK / BFSK phasor (its tones on `carrier`: a Carrier, a Freq, a float, or
+    None for a baseband stream) or (2^bps,) float32 tone frequencies in radians per sample.
+    `process(x, scale)` returns (sym, llr) for the floor((carried + n) / sps) symbols the call
+    completes — the < sps samples left over carry into the next call — on the side of the input;
+    `want_energy=True` (or `out_energy`) adds the (k, 2^bps) float32 energies as a third value."""
+
+    def __init__(self, omega_or_phasor, sps: int, carrier=None, in_dtype: int = DTYPE_F32,
+                 llr_dtype: int = DTYPE_F32, device: int = 0):
+        if isinstance(omega_or_phasor, _Phasor):
+            ph = omega_or_phasor
+            if not isinstance(ph, (MFSK, BFSK)):
+                raise ModemError(ERR_UNSUPPORTED, f"{type(ph).__name__}: no tone-bank detector")
+            omega = ph.tones(carrier)
+        else:
+            omega = omega_or_phasor
+        self.omega = np.ascontiguousarray(omega, dtype=np.float32).reshape(-1)
+        n = self.omega.shape[0]
+        bps = n.bit_length() - 1
+        if n < 2 or n != 1 << bps:
+            raise ModemPanic(ERR_INVALID_ARG, f"ToneDetector: {n} tones are not 2^bps")
+        self.bps, self.sps, self.in_dtype, self.llr_dtype, self.device = bps, int(sps), in_dtype, llr_dtype, device
+        if self.sps < 1:
+            raise ModemPanic(ERR_INVALID_ARG, "ToneDetector: samples per symbol < 1")
+        h = ctypes.c_void_p()
+        _check(load_library().modem_fsk_create(_fptr(self.omega), bps, self.sps, in_dtype, llr_dtype, device,
+                                               ctypes.byref(h)), "ToneDetector")
+        self._h = h
+        self._ncarry = 0
+
+    def nsymbols(self, n: int) -> int:
+        return (self._ncarry + int(n)) // self.sps
+
+    def process(self, x, scale: float = 1.0, out_sym=None, out_llr=None, out_energy=None, want_energy: bool = False,
+                stream=None):
+        n = _check_rx_input(x, self.in_dtype, "ToneDetector.process")
+        k = self.nsymbols(n)
+        sym = out_sym if out_sym is not None else _empty_like_input(x, (k,), np.uint8)
+        llr = out_llr if out_llr is not None else _empty_like_input(x, (k, self.bps), _LLR_DTYPE[self.llr_dtype])
+        en = out_energy if out_energy is not None else (
+            _empty_like_input(x, (k, 1 << self.bps), np.float32) if want_energy else None)
+        cap = min(_check_out(sym, np.uint8, "ToneDetector.process: out_sym"),
+                  _check_out(llr, _LLR_DTYPE[self.llr_dtype], "ToneDetector.process: out_llr") // self.bps)
+        if en is not None:
+            cap = min(cap, _check_out(en, np.float32, "ToneDetector.process: out_energy") >> self.bps)
+        prod = ctypes.c_size_t()
+        _check(load_library().modem_fsk_process(self._h, _ptr(x), n, float(scale), _ptr(sym), _ptr(llr), _ptr(en),
+                                                cap, ctypes.byref(prod), _stream_handle(stream, self.device)),
+               "ToneDetector.process")
+        self._ncarry = (self._ncarry + n) % self.sps
+        p = prod.value
+        res = tuple(a if int(a.shape[0]) == p else a[:p] for a in ((sym, llr) if en is None else (sym, llr, en)))
+        return res
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.modem_fsk_destroy(self._h)
             self._h = None
 
 

@@ -16,6 +16,7 @@
 // result equals the flat form's (every point into bps of the 2*bps minima) bit for bit, at
 // 3 v_min_f32 per point instead of bps. Everything is indexed at compile time: no scratch.
 #include "modem_device.h"
+#include "modem_llr_store.h"
 
 namespace mk {
 
@@ -63,51 +64,6 @@ __device__ __forceinline__ void demap_bits(const Leaf& leaf, float scale, float*
     (void)demap_tree<NB, NB>(leaf, 0, m0, m1);
 #pragma unroll
     for (int j = 0; j < NB; ++j) llr[j] = scale * (m1[j] - m0[j]);
-}
-
-// A lane's BPS outputs as packed 32-bit words (element e at byte e * sizeof(OutT)).
-template <typename OutT> struct DemapOut;
-template <> struct DemapOut<float> {
-    static constexpr int esz = 4;
-    static __device__ __forceinline__ uint32_t bits(float v) { return __float_as_uint(v); }
-};
-template <> struct DemapOut<__half> {   // round to nearest, saturating: never inf
-    static constexpr int esz = 2;
-    static __device__ __forceinline__ uint32_t bits(float v) {
-        const float c = __builtin_fminf(__builtin_fmaxf(v, -65504.f), 65504.f);
-        return (uint32_t)__half_as_ushort(__float2half_rn(c));
-    }
-};
-template <> struct DemapOut<int8_t> {   // rint(clamp(v, -127, 127))
-    static constexpr int esz = 1;
-    static __device__ __forceinline__ uint32_t bits(float v) {
-        const float c = __builtin_fminf(__builtin_fmaxf(v, -127.f), 127.f);
-        return (uint32_t)(int)__builtin_rintf(c) & 0xffu;
-    }
-};
-
-typedef uint32_t demap_u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t demap_u32x4 __attribute__((ext_vector_type(4)));
-
-// The lane's B bytes at dst as B / W stores of W bytes (dst is W-aligned, W divides B).
-template <int W, int B, int NW>
-__device__ __forceinline__ void demap_store(char* dst, const uint32_t (&w)[NW]) {
-#pragma unroll
-    for (int o = 0; o < B; o += W) {
-        if constexpr (W == 16) {
-            demap_u32x4 v = {w[o / 4], w[o / 4 + 1], w[o / 4 + 2], w[o / 4 + 3]};
-            *reinterpret_cast<demap_u32x4*>(dst + o) = v;
-        } else if constexpr (W == 8) {
-            demap_u32x2 v = {w[o / 4], w[o / 4 + 1]};
-            *reinterpret_cast<demap_u32x2*>(dst + o) = v;
-        } else if constexpr (W == 4) {
-            *reinterpret_cast<uint32_t*>(dst + o) = w[o / 4];
-        } else if constexpr (W == 2) {
-            *reinterpret_cast<uint16_t*>(dst + o) = (uint16_t)(w[o / 4] >> (8 * (o % 4)));
-        } else {
-            *reinterpret_cast<uint8_t*>(dst + o) = (uint8_t)(w[o / 4] >> (8 * (o % 4)));
-        }
-    }
 }
 
 // in_f16: f16 I/Q (widened exactly); pair: the (i, q) pairs are naturally aligned (one load);

@@ -200,6 +200,47 @@ struct DemapParams {
 };
 // out_dtype: 0 f32, 1 f16 (saturating), 3 i8 (rint of the value clamped to +-127)
 hipError_t launch_demap(const DemapParams& p, bool axis, int in_dtype, int out_dtype, hipStream_t s);
+// Noncoherent detectors (modem_noncoh.hip). out_dtype as launch_demap's; either output may be null.
+// Differential detector: z[k] = r[k] * conj(r[k-1]), c(s) = z.re * tab[2s] + z.im * tab[2s+1];
+// r[-1] = *prev, and the lane of symbol nsym-1 leaves r[nsym-1] (widened to f32) in *prev_new.
+struct DiffParams {
+    const void* iq;          // nsym interleaved (i, q), f32 or f16
+    const float2* prev;      // the point before iq[0] (device)
+    float2* prev_new;        // the point before the next call's iq[0] (the handle's other slot)
+    const float* tab;        // 2^bps (cos, sin) pairs (device)
+    uint8_t* sym;            // nsym decisions
+    void* llr;               // nsym * bps values, MSB first
+    int64_t nsym;
+    float scale;
+    int32_t bps;
+};
+hipError_t launch_diff(const DiffParams& p, int in_dtype, int out_dtype, hipStream_t s);
+// Tone-bank energy detector: symbol k of this call covers the samples [k*sps, (k+1)*sps) of the
+// logical stream `carry` (ncarry < sps samples) followed by `in` (n samples); the samples after
+// the last whole symbol go to carry_new. tw: the twiddles e^{-j omega[m] i} as (cos, -sin), tone m
+// at sample i in entry fsk_tw_index(bps, sps, m, i): tones in groups of kFskTM, a group's tones
+// of one sample contiguous (a wave works on one group: wave-uniform, scalar loads).
+constexpr int kFskTM = 16;
+constexpr size_t fsk_tw_index(int bps, int sps, int m, int i) {
+    const int M = 1 << bps, TM = M < kFskTM ? M : kFskTM;
+    return ((size_t)(m / TM) * sps + i) * TM + m % TM;
+}
+struct FskParams {
+    const void* in;          // n complex samples, f32 or f16
+    const void* carry;       // ncarry samples of the same dtype
+    void* carry_new;
+    const float2* tw;
+    uint8_t* sym;            // nsym decisions
+    void* llr;               // nsym * bps values, MSB first
+    float* energy;           // nsym * 2^bps tone energies
+    int64_t n;
+    int64_t nsym;            // whole symbols in carry + in
+    int32_t ncarry;
+    int32_t sps;
+    int32_t bps;
+    float scale;
+};
+hipError_t launch_fsk(const FskParams& p, int in_dtype, int out_dtype, hipStream_t s);
 hipError_t launch_phases(float w, uint64_t s0, size_t n, float* out, hipStream_t s);
 hipError_t launch_prng_bits(uint64_t seed, uint8_t* out, size_t nbits, hipStream_t s);
 
