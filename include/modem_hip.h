@@ -61,7 +61,7 @@ extern "C" {
  * added later, additive); 6: modem_chain_batch_* (additive, no layout change; modem_demap_* and
  * MODEM_DTYPE_I8 added later, additive: no descriptor, no layout change; modem_tx_scan_states
  * and modem_tx_scan_path likewise; modem_phasor_diff_lut, modem_phasor_tones, modem_diff_* and
- * modem_fsk_* likewise). Layouts: INTEGRATION.md. */
+ * modem_fsk_* likewise; modem_chan_* and modem_count_errors likewise). Layouts: INTEGRATION.md. */
 #define MODEM_HIP_ABI_VERSION 6
 
 typedef enum {
@@ -453,6 +453,69 @@ modem_status modem_fsk_create(const float* omega, uint32_t bits_per_symbol, uint
 modem_status modem_fsk_process(modem_fsk* h, const void* in, size_t n, float scale, uint8_t* out_sym,
                                void* llr, float* energy, size_t cap, size_t* produced, void* stream);
 modem_status modem_fsk_destroy(modem_fsk* h);
+
+/* ---- Channel model (GLUE: the reference has no channel) ------------------------------------ */
+/* The stage between modem_tx_process and modem_rx_process: gain, an NCO frequency / phase offset
+ * and seeded additive white Gaussian noise on a buffer of interleaved complex samples. For the
+ * absolute sample index n (the handle's s0 plus the position in the stream) and the input x[n]:
+ *
+ *   y[n] = gain * x[n] * e^{j*theta[n]} + sqrt(n0) * w[n]
+ *
+ * NCO, exact for any n:
+ *   theta[n] = 2*pi * ((phase0 + step*n) mod 2^64) / 2^64
+ * phase0 and step are uint64_t, fixed at create time from the doubles `phase` (radians) and `cfo`
+ * (radians per sample; both may be negative): each value v becomes frac(v / (2*pi)) * 2^64, rounded
+ * to nearest and wrapped mod 2^64 (evaluated with enough bits of pi for every finite double).
+ * modem_chan_nco reads the two integers back; they, not the doubles, define the rotation, which
+ * therefore neither degrades at large n nor depends on where the calls cut the stream.
+ *
+ * Noise, counter-based on n, with mix() the splitmix64 finaliser of modem_prng_bits
+ * (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31),
+ * GOLDEN = 0x9E3779B97F4A7C15 and uint64 wrap-around arithmetic:
+ *   k     = mix(seed + GOLDEN)                    the first word modem_prng_bits emits for `seed`
+ *   word  = mix(k + (n+1)*GOLDEN)
+ *   u1    = ((word >> 40) + 1) * 2^-24            in (0, 1], exact in f32
+ *   u2    = ((word & 0xffffffff) >> 8) * 2^-24    in [0, 1), exact in f32
+ *   w[n]  = sqrt(-ln u1) * (cos 2*pi*u2, sin 2*pi*u2)
+ * E|w|^2 = 1: n0 is the complex noise variance (n0/2 per rail), the N0 of the scale = 1/N0 that
+ * modem_demap_process, modem_diff_process and modem_fsk_process document. For a unit-energy matched
+ * filter and symbols of mean energy A^2 carrying bps bits, Eb/N0 = A^2 / (bps * n0).
+ * Limit: |w| <= sqrt(24 ln 2) ~ 4.08 (u1 >= 2^-24), so the tail is cut at about 5.8 per-rail sigma.
+ *
+ * Arithmetic: everything after the integer parts is f32 (the angle from the top 32 bits of the
+ * phase). F16 input is widened exactly; F16 output is rounded to nearest even, as the TX stores it
+ * (beyond the f16 range: unspecified). NaN input: unspecified output. With n0 == 0 no noise is
+ * evaluated; with step == 0 and phase0 == 0 no rotation; with gain == 1 as well the output equals
+ * the input as values (a -0 may become +0).
+ *
+ * Streaming: the handle's only stream state is the sample counter; cutting a buffer into several
+ * calls at any positions, calls with n == 0 included, gives bit-identical output. */
+typedef struct modem_chan modem_chan;
+/* gain, phase, cfo finite; n0 finite and >= 0; in_dtype, out_dtype F32 or F16 (any of the four
+ * pairs), else INVALID_ARG. The handle owns no device memory, so creating it touches no device:
+ * device < 0 is NO_DEVICE here, any other ordinal is checked by the first modem_chan_process. */
+modem_status modem_chan_create(double gain, double phase, double cfo, double n0, uint64_t seed, uint64_t s0,
+                               int32_t in_dtype, int32_t out_dtype, int device, modem_chan** out);
+/* in: n interleaved (i,q) of in_dtype; out: n of out_dtype; cap in samples (cap < n: CAPACITY,
+ * nothing written, the state unchanged); n == 0 is valid. out == in (in place) is allowed when the
+ * dtypes are equal; any other overlap of the two byte ranges, or a stream that would pass sample
+ * 2^64: INVALID_ARG. Device or host pointers, as modem_demap_process. */
+modem_status modem_chan_process(modem_chan* h, const void* in, size_t n, void* out, size_t cap, void* stream);
+/* A new noise variance from the next call on (Eb/N0 sweeps over one stream). */
+modem_status modem_chan_set_n0(modem_chan* h, double n0);
+/* The NCO integers (either pointer may be NULL). */
+modem_status modem_chan_nco(const modem_chan* h, uint64_t* step, uint64_t* phase0);
+/* The n of the next input sample (0 for NULL). */
+uint64_t modem_chan_sample(const modem_chan* h);
+modem_status modem_chan_destroy(modem_chan* h);
+
+/* Error counter for one-byte-per-bit or one-byte-per-symbol decisions:
+ *   counts[0] += #{i < n : a[i] != b[i]}          counts[1] += sum_{i<n} popcount(a[i] ^ b[i])
+ * counts points to two uint64_t that are accumulated into, never cleared: the caller zeroes them.
+ * a, b and counts are all device pointers (asynchronous on `stream`; counts 8-byte aligned) or all
+ * host pointers (synchronous); a mix: INVALID_ARG. */
+modem_status modem_count_errors(const uint8_t* a, const uint8_t* b, size_t n, uint64_t* counts, int device,
+                                void* stream);
 
 /* ---- synthetic input (GLUE): splitmix64 bit stream, one byte per bit ------------------- */
 /* bit i = (word[i/64] >> (i%64)) & 1, word j = splitmix64 output j+1 from `seed`.

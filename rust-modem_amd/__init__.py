@@ -38,6 +38,7 @@ __all__ = [
     "TxBatchPlan", "RxBatchPlan", "SLICER_NONE", "SLICER_NEAREST", "SLICER_QAM_AXIS", "DTYPE_F32", "DTYPE_F16", "DTYPE_I16",
     "SoftDemapper", "DTYPE_I8", "DEMAP_AUTO", "DEMAP_GENERAL",
     "DiffDetector", "ToneDetector",
+    "Channel", "count_errors",
 ]
 
 PI32 = float(np.float32(math.pi))      # std::f32::consts::PI
@@ -179,6 +180,14 @@ def load_library():
         "modem_fsk_create": (st, [fp, u32, u32, c.c_int32, c.c_int32, c.c_int, c.POINTER(vp)]),
         "modem_fsk_process": (st, [vp, vp, sz, f32, vp, vp, vp, sz, c.POINTER(sz), vp]),
         "modem_fsk_destroy": (st, [vp]),
+        "modem_chan_create": (st, [c.c_double, c.c_double, c.c_double, c.c_double, u64, u64, c.c_int32, c.c_int32,
+                                   c.c_int, c.POINTER(vp)]),
+        "modem_chan_process": (st, [vp, vp, sz, vp, sz, vp]),
+        "modem_chan_set_n0": (st, [vp, c.c_double]),
+        "modem_chan_nco": (st, [vp, c.POINTER(u64), c.POINTER(u64)]),
+        "modem_chan_sample": (u64, [vp]),
+        "modem_chan_destroy": (st, [vp]),
+        "modem_count_errors": (st, [vp, vp, sz, vp, c.c_int, vp]),
         "modem_chain_create": (st, [vp, vp, vp, sz, vp, sz, vp, vp, sz, c.POINTER(vp)]),
         "modem_chain_run": (st, [vp, c.POINTER(sz), c.POINTER(sz), vp]),
         "modem_chain_fused": (c.c_int, [vp]),
@@ -1319,6 +1328,81 @@ class ChainBatchPlan:
         if getattr(self, "_h", None) and _lib is not None:
             _lib.modem_chain_batch_destroy(self._h)
             self._h = None
+
+
+# ------------------------------------------------------------------ channel model ----
+class Channel:
+    """Channel model (GLUE: the reference has none) between `DigitalModulator.process` and
+    `DemodulatorRx.process`: y[n] = gain * x[n] * e^{j theta[n]} + sqrt(n0) * w[n] on (n, 2) I/Q.
+
+    theta[n] = 2 pi ((phase0 + step n) mod 2^64) / 2^64 with the uint64 pair `nco` = (step, phase0)
+    derived from `cfo` (radians per sample) and `phase` (radians); w[n] is a unit-variance complex
+    Gaussian that depends only on `seed` and the absolute sample index n (`s0` plus the position in
+    the stream), so any cut of a stream into calls gives the same bytes. n0 is the complex noise
+    variance: pass scale = 1/n0 to the demapper and the detectors. `process(x)` takes a CUDA tensor
+    (asynchronous on the current stream) or a numpy array and returns the result on the same side;
+    `out=x` works in place when the dtypes are equal."""
+
+    def __init__(self, gain: float = 1.0, phase: float = 0.0, cfo: float = 0.0, n0: float = 0.0, seed: int = 0,
+                 s0: int = 0, in_dtype: int = DTYPE_F32, out_dtype: int = DTYPE_F32, device: int = 0):
+        if not 0 <= int(seed) < 1 << 64 or not 0 <= int(s0) < 1 << 64:
+            raise ModemPanic(ERR_INVALID_ARG, "Channel: seed and s0 are uint64")
+        self.in_dtype, self.out_dtype, self.device = in_dtype, out_dtype, device
+        h = ctypes.c_void_p()
+        _check(load_library().modem_chan_create(float(gain), float(phase), float(cfo), float(n0), int(seed), int(s0),
+                                                in_dtype, out_dtype, device, ctypes.byref(h)), "Channel")
+        self._h = h
+
+    def process(self, x, out=None, stream=None):
+        n = _check_rx_input(x, self.in_dtype, "Channel.process")
+        np_dtype = _LLR_DTYPE[self.out_dtype]
+        y = out if out is not None else _empty_like_input(x, (n, 2), np_dtype)
+        cap = _check_out(y, np_dtype, "Channel.process: out") // 2
+        _check(load_library().modem_chan_process(self._h, _ptr(x), n, _ptr(y), cap,
+                                                 _stream_handle(stream, self.device)), "Channel.process")
+        return y
+
+    def set_n0(self, n0: float) -> None:
+        _check(load_library().modem_chan_set_n0(self._h, float(n0)), "Channel.set_n0")
+
+    @property
+    def nco(self) -> Tuple[int, int]:
+        step, phase0 = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(load_library().modem_chan_nco(self._h, ctypes.byref(step), ctypes.byref(phase0)), "Channel.nco")
+        return int(step.value), int(phase0.value)
+
+    @property
+    def sample(self) -> int:
+        return int(load_library().modem_chan_sample(self._h))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.modem_chan_destroy(self._h)
+            self._h = None
+
+
+def count_errors(a, b, counts=None, stream=None, device: int = 0):
+    """counts[0] += #{i: a[i] != b[i]}, counts[1] += sum_i popcount(a[i] ^ b[i]) over two uint8
+    buffers of one size (bits, one byte each, or symbols), both CUDA tensors (asynchronous on the
+    current stream; no host copy) or both numpy arrays. `counts`: a 2-element int64 tensor / array
+    on the same side to accumulate into, or None for a zeroed one. Returns it."""
+    if _is_torch(a) != _is_torch(b) or (counts is not None and _is_torch(counts) != _is_torch(a)):
+        raise ModemPanic(ERR_INVALID_ARG, "count_errors: a, b and counts must be on one side")
+    n = _check_out(a, np.uint8, "count_errors: a")
+    if _check_out(b, np.uint8, "count_errors: b") != n:
+        raise ModemPanic(ERR_INVALID_ARG, "count_errors: a and b differ in size")
+    if counts is None:
+        if _is_torch(a):
+            import torch
+            counts = torch.zeros(2, dtype=torch.int64, device=a.device)
+        else:
+            counts = np.zeros(2, dtype=np.int64)
+    elif _check_out(counts, np.int64, "count_errors: counts") != 2:
+        raise ModemPanic(ERR_INVALID_ARG, "count_errors: counts must have 2 elements")
+    device = _device_of(a, device)
+    _check(load_library().modem_count_errors(_ptr(a) if n else None, _ptr(b) if n else None, n, _ptr(counts), device,
+                                             _stream_handle(stream, device)), "count_errors")
+    return counts
 
 
 def prng_bits(seed: int, nbits: int, device: int = 0, stream=None):

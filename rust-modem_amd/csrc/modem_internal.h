@@ -241,6 +241,25 @@ struct FskParams {
     float scale;
 };
 hipError_t launch_fsk(const FskParams& p, int in_dtype, int out_dtype, hipStream_t s);
+// Channel model (modem_chan.hip): y = gain * x * e^{j theta} + sig * w for the n samples of one call,
+// passed by value. cnt0 = k + (n_abs + 1) * GOLDEN and ph0 = phase0 + step * n_abs for the call's
+// first sample n_abs (64-bit wrap-around); align is set by the launcher (2: both buffers 16-byte
+// aligned, 1: sample-aligned, 0: element-aligned).
+struct ChanParams {
+    const void* in;          // n interleaved (i, q), f32 or f16
+    void* out;               // n interleaved (i, q), f32 or f16; may equal `in` when the dtypes do
+    int64_t n;
+    uint64_t cnt0;
+    uint64_t ph0;
+    uint64_t step;
+    float gain;
+    float sig;               // sqrt(n0)
+    int32_t align;
+};
+// noise: sig != 0; rot: step != 0 or phase0 != 0. dtypes: 0 f32, 1 f16.
+hipError_t launch_chan(const ChanParams& p, bool noise, bool rot, int in_dtype, int out_dtype, hipStream_t s);
+// counts[0] += #{i: a[i] != b[i]}, counts[1] += sum popcount(a[i] ^ b[i]) (device pointers)
+hipError_t launch_count_errors(const uint8_t* a, const uint8_t* b, size_t n, uint64_t* counts, hipStream_t s);
 hipError_t launch_phases(float w, uint64_t s0, size_t n, float* out, hipStream_t s);
 hipError_t launch_prng_bits(uint64_t seed, uint8_t* out, size_t nbits, hipStream_t s);
 
