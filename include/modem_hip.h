@@ -61,7 +61,8 @@ extern "C" {
  * added later, additive); 6: modem_chain_batch_* (additive, no layout change; modem_demap_* and
  * MODEM_DTYPE_I8 added later, additive: no descriptor, no layout change; modem_tx_scan_states
  * and modem_tx_scan_path likewise; modem_phasor_diff_lut, modem_phasor_tones, modem_diff_* and
- * modem_fsk_* likewise; modem_chan_* and modem_count_errors likewise). Layouts: INTEGRATION.md. */
+ * modem_fsk_* likewise; modem_chan_* and modem_count_errors likewise;
+ * modem_sync_* likewise). Layouts: INTEGRATION.md. */
 #define MODEM_HIP_ABI_VERSION 6
 
 typedef enum {
@@ -516,6 +517,74 @@ modem_status modem_chan_destroy(modem_chan* h);
  * host pointers (synchronous); a mix: INVALID_ARG. */
 modem_status modem_count_errors(const uint8_t* a, const uint8_t* b, size_t n, uint64_t* counts, int device,
                                 void* stream);
+
+/* ---- Carrier synchronizer (GLUE: the reference has none) ----------------------------------- */
+/* A non-data-aided feedforward carrier synchronizer at symbol rate, on the decimated I/Q that
+ * modem_rx_process writes and in front of modem_demap_process or a slicer: block M-th-power
+ * (Viterbi & Viterbi) phase estimates, unwrapped across blocks, applied as a piecewise-linear
+ * derotation. It removes what modem_chan_create's `phase` and `cfo` put in.
+ *
+ * Parameters: power = M in {2, 4, 8}, the constellation's rotational symmetry (lm = log2 M);
+ * block = B, symbols per block, a power of two in 64 .. 4096 (lb = log2 B); norm, a finite double
+ * > 0 applied (as f32) before the power, 1 / rms of the constellation; ref_phase, the argument of
+ * sum_s (norm * lut[s])^M over the constellation (pi for square QAM), and phase0, where the tracker
+ * starts, finite doubles in radians turned into uint64 fractions of a turn exactly as
+ * modem_chan_create turns `phase` into phase0 (`ref`, `phase0` below); flags: MODEM_SYNC_FLAT.
+ *
+ * For the stream's symbols r[k], k counted from the handle's first input symbol (after a flush:
+ * from the first symbol after it), block b covers k = b*B .. b*B + B-1.
+ *
+ * 1. Per block, in f32:  z[k] = (norm * r[k])^M by lm complex squarings ((a, b) -> (a*a - b*b,
+ *    2*a*b)), |z[k]| = (|norm * r[k]|^2)^(M/2), P_b = sum z[k], S_b = sum |z[k]|. The summation
+ *    order depends on the offset i = k - b*B alone, never on where calls cut the stream: the terms
+ *    with the same i mod 256 are added with i ascending, starting from 0 (at most 16 terms); for
+ *    each l = i mod 64 the four sums of i mod 256 = l, l+64, l+128, l+192 are joined as
+ *    (t0 + t1) + (t2 + t3); the 64 results are joined by a balanced tree that pairs l with
+ *    l xor 32, then xor 16, 8, 4, 2, 1.
+ * 2. q_b = |P_b| / S_b, 0 when S_b is 0 or anything is not finite.
+ *    Phi_b = ((uint64_t)turn(P_b.im, P_b.re) << 32) - ref, where turn(y, x) is atan2(y, x) as a
+ *    32-bit fraction of a turn, within 2^-22 turns of the exact angle; turn(0, 0) and non-finite
+ *    input give 0.
+ * 3. Unwrap, exact in uint64 / int64 ring arithmetic (sext64: the value read as int64; >> on it
+ *    arithmetic):
+ *      theta_b = theta_{b-1} + (sext64(Phi_b - Phi_{b-1}) >> lm)
+ *      theta_{-1} = phase0,  Phi_{-1} = M * phase0 mod 2^64
+ *    so theta_0 is the branch of Phi_0 / M nearest phase0. The M-fold ambiguity is inherent: the
+ *    estimator cannot tell a carrier phase from one a multiple of 1/M turn away, so the output is
+ *    the constellation up to the rotation that phase0 selects, and a block whose estimate is off by
+ *    more than 1/(2M) turn moves every later block by 1/M turn (a slip). Tracking range: the phase
+ *    may advance by less than 1/(2M) turn per block, |cfo per symbol| < pi / (M * B) radians.
+ * 4. Apply:  d_b = sext64(theta_b - theta_{b-1}), d_0 = 0 for the stream's first block;
+ *    s_b = d_b >> (lb + 1), 0 under MODEM_SYNC_FLAT; for the offset i in block b
+ *      ph = theta_b + s_b * (2*i - B + 1) mod 2^64         (theta_b at the block's centre)
+ *      out[k] = r[k] * e^{-j*2*pi*ph / 2^64}
+ *    from the top 32 bits of ph, in f32. F16 input is widened exactly, F16 output rounded to
+ *    nearest even.
+ * 5. Streaming: the handle carries, on the device, the < B symbols after the last whole block and
+ *    theta, Phi, d of the last block. A call emits floor((carried + n) / B) blocks; any cut of a
+ *    stream into calls, nsym == 0 included, gives bit-identical out, theta and quality.
+ *    modem_sync_flush emits the carried symbols rotated on the last block's line extended
+ *    (i -> i + B), or by phase0 (theta = phase0, s = 0) when no block was ever completed; it writes
+ *    no estimates, and the handle is at a block boundary afterwards (theta, Phi and d stay). */
+#define MODEM_SYNC_FLAT 1u        /* one phase per block (s_b = 0) instead of the line through the centres */
+typedef struct modem_sync modem_sync;
+/* Bad power, block, norm, phases, flags, dtypes (F32 or F16, any of the four pairs) or a NULL out:
+ * INVALID_ARG, before any device is looked at. The handle owns device memory: a bad ordinal is
+ * NO_DEVICE here. */
+modem_status modem_sync_create(uint32_t power, uint32_t block, double norm, double ref_phase, double phase0,
+                               uint32_t flags, int32_t in_dtype, int32_t out_dtype, int device, modem_sync** out);
+/* iq: nsym interleaved (i,q) of in_dtype; out: *produced = *blocks * B symbols of out_dtype, cap in
+ * symbols; theta (uint64_t) and quality (float), one per block, either may be NULL, est_cap in
+ * blocks. cap or est_cap too small: CAPACITY, nothing written, the state unchanged. The output lags
+ * the input by the carried symbols, so there is no in-place form: overlapping byte ranges of iq
+ * and out are INVALID_ARG. Device or host pointers, as modem_demap_process. */
+modem_status modem_sync_process(modem_sync* h, const void* iq, size_t nsym, void* out, size_t cap, uint64_t* theta,
+                                float* quality, size_t est_cap, size_t* produced, size_t* blocks, void* stream);
+/* The carried symbols (*produced < B of them); cap in symbols, too small: CAPACITY as above. */
+modem_status modem_sync_flush(modem_sync* h, void* out, size_t cap, size_t* produced, void* stream);
+/* The number of input symbols taken so far (0 for NULL). */
+uint64_t modem_sync_symbol(const modem_sync* h);
+modem_status modem_sync_destroy(modem_sync* h);
 
 /* ---- synthetic input (GLUE): splitmix64 bit stream, one byte per bit ------------------- */
 /* bit i = (word[i/64] >> (i%64)) & 1, word j = splitmix64 output j+1 from `seed`.

@@ -39,6 +39,7 @@ __all__ = [
     "SoftDemapper", "DTYPE_I8", "DEMAP_AUTO", "DEMAP_GENERAL",
     "DiffDetector", "ToneDetector",
     "Channel", "count_errors",
+    "CarrierSync", "SYNC_FLAT",
 ]
 
 PI32 = float(np.float32(math.pi))      # std::f32::consts::PI
@@ -48,6 +49,7 @@ MODEM_OK, ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_NO_DEVICE, ERR_CAPACITY
 DTYPE_F32, DTYPE_F16, DTYPE_I16 = 0, 1, 2   # I16: real samples, RX input (demodulate)
 DTYPE_I8 = 3                                # only as SoftDemapper's out_dtype
 DEMAP_AUTO, DEMAP_GENERAL = 0, 1
+SYNC_FLAT = 1                               # CarrierSync flags: one phase per block
 OUT_IQ_MIXED, OUT_IQ_BASEBAND, OUT_REAL = 0, 1, 2
 MIX_COMPLEX, MIX_REFERENCE_REAL, MIX_REFERENCE_REAL_EXACT = 0, 1, 2
 SLICER_NONE, SLICER_NEAREST, SLICER_QAM_AXIS = 0, 1, 2
@@ -188,6 +190,12 @@ def load_library():
         "modem_chan_sample": (u64, [vp]),
         "modem_chan_destroy": (st, [vp]),
         "modem_count_errors": (st, [vp, vp, sz, vp, c.c_int, vp]),
+        "modem_sync_create": (st, [u32, u32, c.c_double, c.c_double, c.c_double, u32, c.c_int32, c.c_int32, c.c_int,
+                                   c.POINTER(vp)]),
+        "modem_sync_process": (st, [vp, vp, sz, vp, sz, vp, vp, sz, c.POINTER(sz), c.POINTER(sz), vp]),
+        "modem_sync_flush": (st, [vp, vp, sz, c.POINTER(sz), vp]),
+        "modem_sync_symbol": (u64, [vp]),
+        "modem_sync_destroy": (st, [vp]),
         "modem_chain_create": (st, [vp, vp, vp, sz, vp, sz, vp, vp, sz, c.POINTER(vp)]),
         "modem_chain_run": (st, [vp, c.POINTER(sz), c.POINTER(sz), vp]),
         "modem_chain_fused": (c.c_int, [vp]),
@@ -334,6 +342,13 @@ class _Phasor:
         """SoftDemapper over this phasor's table (in_dtype, out_dtype, path, device)."""
         return SoftDemapper(self, **kw)
 
+    def synchronizer(self, block: int = 256, **kw) -> "CarrierSync":
+        """CarrierSync for this constellation: norm = 1 / rms of the table, M the smallest of 2, 4, 8
+        whose M-th power leaves a line, |sum_s (norm lut_s)^M| / sum_s |norm lut_s|^M >= 0.25, and
+        ref_phase the argument of that sum (float64). Further keywords go to CarrierSync."""
+        power, norm, ref = _sync_params(self.lut(), type(self).__name__)
+        return CarrierSync(power, block, norm, ref, **kw)
+
     def detector(self, *args, **kw):
         """The noncoherent detector of a phasor that carries state from symbol to symbol (DMPSK,
         MFSK, BFSK); every other phasor is received through slicer() / demapper()."""
@@ -433,6 +448,9 @@ class _SamplePhasor(_Phasor):
 
     def demapper(self, **kw):
         raise ModemError(ERR_UNSUPPORTED, f"{type(self).__name__}: no memoryless demapper")
+
+    def synchronizer(self, *args, **kw):
+        raise ModemError(ERR_UNSUPPORTED, f"{type(self).__name__}: no table to derive a carrier synchronizer from")
 
     def i(self, s, b):
         raise ModemError(ERR_UNSUPPORTED, "evaluated per sample inside DigitalModulator")
@@ -1378,6 +1396,94 @@ class Channel:
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.modem_chan_destroy(self._h)
+            self._h = None
+
+
+# ------------------------------------------------------------ carrier synchronizer ----
+def _sync_params(lut, what: str = "synchronizer"):
+    """(M, norm, ref_phase) of a constellation table: see _Phasor.synchronizer."""
+    z = np.asarray(lut, dtype=np.float64).reshape(-1, 2)
+    z = z[:, 0] + 1j * z[:, 1]
+    ms = float(np.mean(np.abs(z) ** 2))
+    if not ms > 0.0 or not math.isfinite(ms):
+        raise ModemPanic(ERR_INVALID_ARG, f"{what}: a table without energy")
+    norm = 1.0 / math.sqrt(ms)
+    for power in (2, 4, 8):
+        p = (norm * z) ** power
+        line = complex(p.sum())
+        if abs(line) / float(np.abs(p).sum()) >= 0.25:
+            return power, norm, math.atan2(line.imag, line.real)
+    raise ModemPanic(ERR_INVALID_ARG, f"{what}: no power of 2, 4, 8 leaves a spectral line of this constellation")
+
+
+class CarrierSync:
+    """Feedforward carrier synchronizer (GLUE: the reference has none) at symbol rate, on the (n, 2)
+    I/Q that `DemodulatorRx.process` returns and in front of the demapper: block M-th-power phase
+    estimates over `block` symbols, unwrapped across blocks, applied as a piecewise-linear
+    derotation (include/modem_hip.h, "Carrier synchronizer"). `power` M in (2, 4, 8); `norm` scales
+    the points before the power; `ref_phase` is the argument of sum_s (norm lut_s)^M; the tracker
+    starts at `phase0`. The constellation comes out up to a multiple of 1/M turn, which `phase0`
+    selects; the offset per symbol must stay below pi / (M block).
+
+    `process(riq)` returns (out, theta, quality) for the floor((carried + n) / block) blocks the
+    call completes: out (blocks * block, 2) of out_dtype, theta (blocks,) the unwrapped phase at
+    each block centre in 2^-64 turns (numpy uint64, or the same bits in a torch int64), quality
+    (blocks,) float32 |P| / S in [0, 1]; the < block symbols left over carry into the next call.
+    `flush()` returns the carried symbols rotated on the last block's line. CUDA tensors
+    (asynchronous on the current stream) or numpy arrays, results on the side of the input."""
+
+    def __init__(self, power: int, block: int = 256, norm: float = 1.0, ref_phase: float = 0.0, phase0: float = 0.0,
+                 flags: int = 0, in_dtype: int = DTYPE_F32, out_dtype: int = DTYPE_F32, device: int = 0):
+        if not 0 <= int(power) < 1 << 32 or not 0 <= int(block) < 1 << 32 or not 0 <= int(flags) < 1 << 32:
+            raise ModemPanic(ERR_INVALID_ARG, "CarrierSync: power, block and flags are uint32")
+        self.power, self.block, self.in_dtype, self.out_dtype, self.device = int(power), int(block), in_dtype, out_dtype, device
+        self.norm, self.ref_phase, self.phase0, self.flags = float(norm), float(ref_phase), float(phase0), int(flags)
+        h = ctypes.c_void_p()
+        _check(load_library().modem_sync_create(self.power, self.block, float(norm), float(ref_phase), float(phase0),
+                                                int(flags), in_dtype, out_dtype, device, ctypes.byref(h)), "CarrierSync")
+        self._h = h
+        self._ncarry = 0
+
+    def nblocks(self, n: int) -> int:
+        return (self._ncarry + int(n)) // self.block
+
+    def process(self, riq, out=None, stream=None):
+        n = _check_rx_input(riq, self.in_dtype, "CarrierSync.process")
+        nb = self.nblocks(n)
+        np_dtype = _LLR_DTYPE[self.out_dtype]
+        y = out if out is not None else _empty_like_input(riq, (nb * self.block, 2), np_dtype)
+        cap = _check_out(y, np_dtype, "CarrierSync.process: out") // 2
+        if _is_torch(riq):
+            import torch
+            theta = torch.empty(nb, dtype=torch.int64, device=riq.device)
+            q = torch.empty(nb, dtype=torch.float32, device=riq.device)
+        else:
+            theta, q = np.empty(nb, np.uint64), np.empty(nb, np.float32)
+        prod, blocks = ctypes.c_size_t(), ctypes.c_size_t()
+        _check(load_library().modem_sync_process(self._h, _ptr(riq) if n else None, n, _ptr(y), cap, _ptr(theta), _ptr(q),
+                                                 nb, ctypes.byref(prod), ctypes.byref(blocks),
+                                                 _stream_handle(stream, self.device)), "CarrierSync.process")
+        self._ncarry = (self._ncarry + n) % self.block
+        p = prod.value
+        return (y if int(y.shape[0]) == p else y[:p]), theta, q
+
+    def flush(self, like=None, stream=None):
+        n = self._ncarry
+        ref = like if like is not None else np.zeros(1, np.float32)
+        y = _empty_like_input(ref, (n, 2), _LLR_DTYPE[self.out_dtype])
+        prod = ctypes.c_size_t()
+        _check(load_library().modem_sync_flush(self._h, _ptr(y), n, ctypes.byref(prod),
+                                               _stream_handle(stream, self.device)), "CarrierSync.flush")
+        self._ncarry = 0
+        return y
+
+    @property
+    def symbol(self) -> int:
+        return int(load_library().modem_sync_symbol(self._h))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.modem_sync_destroy(self._h)
             self._h = None
 
 

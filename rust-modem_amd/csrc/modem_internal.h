@@ -260,6 +260,35 @@ struct ChanParams {
 hipError_t launch_chan(const ChanParams& p, bool noise, bool rot, int in_dtype, int out_dtype, hipStream_t s);
 // counts[0] += #{i: a[i] != b[i]}, counts[1] += sum popcount(a[i] ^ b[i]) (device pointers)
 hipError_t launch_count_errors(const uint8_t* a, const uint8_t* b, size_t n, uint64_t* counts, hipStream_t s);
+// Carrier synchronizer (modem_sync.hip), one modem_sync_process call, passed by value. The logical
+// stream of the call is `carry || in`: ncarry symbols the handle kept, then the n new ones; its
+// first nblk * B symbols are estimated (phi, q), unwrapped (th) and derotated (out), the rest
+// (< B) goes to carry_new. state / state_new: {theta, Phi, d} of the last block before / after the
+// call (d = theta_b - theta_{b-1} as the apply step uses it: 0 for the stream's first block).
+// th has nblk + 1 entries: th[0] = theta before the call, th[1 + b] = theta of the call's block b.
+struct SyncParams {
+    const void* in;          // n interleaved (i, q) of the input dtype
+    const void* carry;       // ncarry symbols of the input dtype, 16-byte aligned
+    void* carry_new;         // the other carry slot
+    void* out;               // nblk * B interleaved (i, q) of the output dtype
+    uint64_t* phi;           // [nblk]     workspace: Phi of every block
+    uint64_t* th;            // [nblk + 1] workspace
+    float* q;                // [nblk]     workspace: quality of every block
+    const uint64_t* state;
+    uint64_t* state_new;
+    int64_t n, nblk;
+    uint64_t ref;            // ref_phase in 2^-64 turns
+    float nrm;
+    int32_t ncarry, lb, lm;
+    int32_t first;           // no block was completed before this call: d of block 0 is 0
+    int32_t flat;            // MODEM_SYNC_FLAT: s = 0
+    int32_t in_align, out_align;   // set by the launcher: 2 = groups of 4 symbols 16-byte aligned, 1 = symbol-aligned, 0 = element-aligned
+};
+constexpr int kSyncState = 3;    // u64 words per state slot
+// est + scan + apply (nblk > 0), or only the move of the leftover into carry_new (nblk == 0)
+hipError_t launch_sync(const SyncParams& p, int in_dtype, int out_dtype, hipStream_t s);
+// flush: the ncarry carried symbols, rotated on the last block's line extended (i -> i + B)
+hipError_t launch_sync_flush(const SyncParams& p, int in_dtype, int out_dtype, hipStream_t s);
 hipError_t launch_phases(float w, uint64_t s0, size_t n, float* out, hipStream_t s);
 hipError_t launch_prng_bits(uint64_t seed, uint8_t* out, size_t nbits, hipStream_t s);
 
