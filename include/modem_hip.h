@@ -181,6 +181,11 @@ modem_status modem_phasor_slicer(const modem_phasor_desc* d, const float* lut,
 /* Root-raised-cosine taps (GLUE, absent from the reference): centred at (L-1)/2,
  * roll-off beta, unit energy. */
 modem_status modem_rrc_taps(uint32_t ntaps, uint32_t sps, double beta, float* out);
+/* The same pulse sampled at t = (i - (ntaps-1)/2 - offset) / sps, offset a finite double in samples
+ * (else INVALID_ARG), normalised to unit energy; offset == 0 is modem_rrc_taps bit for bit. A TX
+ * shaped with these taps is the nominal TX delayed by `offset` samples: how a stream with a
+ * fractional timing offset is made. */
+modem_status modem_rrc_taps_offset(uint32_t ntaps, uint32_t sps, double beta, double offset, float* out);
 
 /* ---- TX: DigitalModulator + pulse shaping ------------------------------------------------ */
 typedef struct modem_tx modem_tx;
@@ -585,6 +590,91 @@ modem_status modem_sync_flush(modem_sync* h, void* out, size_t cap, size_t* prod
 /* The number of input symbols taken so far (0 for NULL). */
 uint64_t modem_sync_symbol(const modem_sync* h);
 modem_status modem_sync_destroy(modem_sync* h);
+
+/* ---- Symbol timing synchronizer (GLUE: the reference has none) ------------------------------ */
+/* A non-data-aided feedforward symbol timing synchronizer at sample rate, on the I/Q that
+ * modem_rx_process writes with decim = 1 (the matched-filter output at N samples per symbol) and in
+ * front of modem_sync_process: block square-law (Oerder & Meyr) delay estimates from the
+ * symbol-rate line of |x|^2, unwrapped across blocks, applied as a piecewise-linear delay through
+ * a 4-tap cubic Lagrange interpolator. It emits one point per symbol, at the centre of the eye.
+ * The estimate is blind to carrier phase and frequency offset. The chain is
+ * rx(decim = 1) -> timing -> carrier synchronizer -> demapper.
+ *
+ * Parameters: sps = N, samples per symbol, 4 or 8 (ln = log2 N); block = B, symbols per block, a
+ * power of two in 32 .. 4096 (lb = log2 B); span, in symbols, 1 .. 16: the tracked delay is kept
+ * within +-span symbols; tau0, a finite double with |tau0| <= span, in symbols, where the tracker
+ * starts: D_{-1} = rint(tau0 * 2^32); flags: MODEM_TIMING_FLAT.
+ *
+ * The input is the stream x[n], n counted from the handle's first input sample (after a flush:
+ * from the first sample after it), x[n] = 0 for n < 0. Block b covers the symbols k = b*B ..
+ * b*B + B-1, that is the samples b*B*N .. (b+1)*B*N - 1. Delays are int64 in units of 2^-32 symbol.
+ *
+ * 1. Per block, in f32:  E_p = sum_{k in block} |x[k*N + p]|^2 for p = 0 .. N-1, each term
+ *    fma(re, re, im*im). The summation order depends on the sample's offset u = n - b*B*N alone,
+ *    never on where calls cut the stream: the terms with the same u mod 512 are added with u
+ *    ascending, starting from 0 (at most 64 terms); for each v = u mod 128 the four sums of
+ *    u mod 512 = v, v+128, v+256, v+384 are joined as (t0 + t1) + (t2 + t3); the 128 / N results
+ *    of one p = v mod N are joined by a balanced tree over l = v / 2 that pairs l with l xor 32,
+ *    then xor 16, 8, 4 (and 2 when N = 4). S_b = (E0 + E1) + (E2 + E3), for N = 8 that plus
+ *    ((E4 + E5) + (E6 + E7)). The symbol-rate line X_b = sum_p E_p e^{-j 2 pi p / N}:
+ *      N = 4:  re = E0 - E2,  im = E3 - E1
+ *      N = 8:  h = (float)sqrt(0.5), d_p = E_p - E_{p+4}:
+ *              re = d0 + h*(d1 - d3),  im = -(d2 + h*(d1 + d3))
+ *    every operation rounded on its own (no contraction).
+ * 2. q_b = |X_b| / S_b, 0 when S_b is 0 or anything is not finite.
+ *    Phi_b = (0 - turn32(X_b.im, X_b.re)) mod 2^32, turn32 the 32-bit angle of the carrier
+ *    synchronizer (within 2^-22 turns; 0 for (0, 0) and non-finite input). Phi_b / 2^32 is the
+ *    fraction of a symbol by which the centre of the eye lags the grid instants k*N.
+ * 3. Unwrap, exact in int64 (sext32: the low 32 bits read as int32):
+ *      D_b = D_{b-1} + sext32(Phi_b - low32(D_{b-1}))
+ *    so D_b is the branch of Phi_b nearest D_{b-1}, and after the first block a prefix sum of
+ *    sext32(Phi_b - Phi_{b-1}). Tracking range: the delay may move by less than half a symbol per
+ *    block. tau[b] = D_b.
+ * 4. Apply:  s_b = (D_b - D_{b-1}) >> (lb + 1) (arithmetic), 0 for the stream's first block and
+ *    under MODEM_TIMING_FLAT; for the offset i in block b
+ *      e  = clamp(D_b + s_b * (2*i - B + 1), -span * 2^32, +span * 2^32)
+ *      Q  = N * ((i - span) * 2^32 + e)        Q32.32 samples relative to sample b*B*N
+ *      m  = Q >> 32 (floor),  mu = ((Q & 0xffffffff) >> 8) * 2^-24   (exact in f32)
+ *      out[b*B + i] = sum_{j=-1..2} c_j(mu) * x[b*B*N + m + j]
+ *    in f32, each component as ((c_-1 * x_-1, then fma(c_0, x_0, .), fma(c_1, x_1, .),
+ *    fma(c_2, x_2, .)), with a = mu + 1, b = mu - 1, d = mu - 2, k6 = (float)(1.0 / 6.0):
+ *      c_-1 = (-((mu*b)*d)) * k6     c_0 = ((a*b)*d) * 0.5
+ *      c_1  = (-((a*mu)*d)) * 0.5    c_2 = ((a*mu)*b) * k6
+ *    so mu = 0 gives exactly (-0, 1, 0, -0) and out = x[b*B*N + m] bit for bit (finite taps). F16
+ *    input is widened exactly, F16 output rounded to nearest even.
+ *    Output symbol k is the input interpolated at the centre of the eye of grid symbol k - span:
+ *    the fixed lag of `span` symbols is what lets block b be emitted the moment its last sample
+ *    arrives. The clamp keeps every tap inside the samples b*B*N - 2*span*N - 1 .. (b+1)*B*N - 1;
+ *    a delay outside +-span gives clamped positions: specified and memory-safe, not right. The
+ *    first `span` outputs of a stream straddle the zeros before it. Which output is a frame's
+ *    first symbol (integer-symbol alignment) stays with the caller.
+ * 5. Streaming: the handle carries, on the device, the 2*span*N + 1 samples before the current
+ *    block, the samples of the incomplete block, and D, Phi, D - D_prev of the last block. A call
+ *    emits floor((carried + n) / (B*N)) blocks; any cut of a stream into calls, n == 0 included,
+ *    gives bit-identical out, tau and quality. modem_timing_flush emits floor(carried / N) symbols
+ *    on the last block's line extended (i -> i + B in e, i in Q), or at D_{-1} with s = 0 when no
+ *    block was ever completed; samples past the end read as zero and the < N trailing samples are
+ *    dropped. It writes no estimates; afterwards the handle is at a block boundary with an all-zero
+ *    history, and D, Phi and D - D_prev stay. */
+#define MODEM_TIMING_FLAT 1u      /* one delay per block (s_b = 0) instead of the line through the centres */
+typedef struct modem_timing modem_timing;
+/* Bad sps, block, span, tau0, flags, dtypes (F32 or F16, any of the four pairs) or a NULL out:
+ * INVALID_ARG, before any device is looked at. The handle owns device memory: a bad ordinal is
+ * NO_DEVICE here. */
+modem_status modem_timing_create(uint32_t sps, uint32_t block, uint32_t span, double tau0, uint32_t flags,
+                                 int32_t in_dtype, int32_t out_dtype, int device, modem_timing** out);
+/* in: n interleaved (i,q) samples of in_dtype; out: *produced = *blocks * B symbols of out_dtype,
+ * cap in symbols; tau (int64_t) and quality (float), one per block, either may be NULL, est_cap in
+ * blocks. cap or est_cap too small: CAPACITY, nothing written, the state unchanged. An output
+ * symbol gathers samples around its position, so there is no in-place form: overlapping byte ranges
+ * of in and out are INVALID_ARG. Device or host pointers, as modem_sync_process. */
+modem_status modem_timing_process(modem_timing* h, const void* in, size_t n, void* out, size_t cap, int64_t* tau,
+                                  float* quality, size_t est_cap, size_t* produced, size_t* blocks, void* stream);
+/* The symbols of the incomplete block (*produced < B of them); cap in symbols, too small: CAPACITY as above. */
+modem_status modem_timing_flush(modem_timing* h, void* out, size_t cap, size_t* produced, void* stream);
+/* The number of input samples taken so far (0 for NULL). */
+uint64_t modem_timing_sample(const modem_timing* h);
+modem_status modem_timing_destroy(modem_timing* h);
 
 /* ---- synthetic input (GLUE): splitmix64 bit stream, one byte per bit ------------------- */
 /* bit i = (word[i/64] >> (i%64)) & 1, word j = splitmix64 output j+1 from `seed`.

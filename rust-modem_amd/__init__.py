@@ -40,6 +40,7 @@ __all__ = [
     "DiffDetector", "ToneDetector",
     "Channel", "count_errors",
     "CarrierSync", "SYNC_FLAT",
+    "TimingSync",
 ]
 
 PI32 = float(np.float32(math.pi))      # std::f32::consts::PI
@@ -150,6 +151,7 @@ def load_library():
         "modem_phasor_lut": (st, [c.POINTER(_PhasorDesc), fp]),
         "modem_phasor_slicer": (st, [c.POINTER(_PhasorDesc), fp, c.POINTER(_SlicerDesc)]),
         "modem_rrc_taps": (st, [u32, u32, c.c_double, fp]),
+        "modem_rrc_taps_offset": (st, [u32, u32, c.c_double, c.c_double, fp]),
         "modem_tx_create": (st, [c.POINTER(_TxDesc), c.c_int, c.POINTER(vp)]),
         "modem_tx_process": (st, [vp, vp, sz, vp, sz, c.POINTER(sz), vp]),
         "modem_tx_flush": (st, [vp, vp, sz, c.POINTER(sz), vp]),
@@ -196,6 +198,11 @@ def load_library():
         "modem_sync_flush": (st, [vp, vp, sz, c.POINTER(sz), vp]),
         "modem_sync_symbol": (u64, [vp]),
         "modem_sync_destroy": (st, [vp]),
+        "modem_timing_create": (st, [u32, u32, u32, c.c_double, u32, c.c_int32, c.c_int32, c.c_int, c.POINTER(vp)]),
+        "modem_timing_process": (st, [vp, vp, sz, vp, sz, vp, vp, sz, c.POINTER(sz), c.POINTER(sz), vp]),
+        "modem_timing_flush": (st, [vp, vp, sz, c.POINTER(sz), vp]),
+        "modem_timing_sample": (u64, [vp]),
+        "modem_timing_destroy": (st, [vp]),
         "modem_chain_create": (st, [vp, vp, vp, sz, vp, sz, vp, vp, sz, c.POINTER(vp)]),
         "modem_chain_run": (st, [vp, c.POINTER(sz), c.POINTER(sz), vp]),
         "modem_chain_fused": (c.c_int, [vp]),
@@ -576,10 +583,11 @@ class BFSK(_SamplePhasor):
     detector = _tone_detector
 
 
-def rrc_taps(ntaps: int, sps: int, beta: float = 0.35) -> np.ndarray:
-    """Root-raised-cosine taps (GLUE: absent from the reference), unit energy."""
+def rrc_taps(ntaps: int, sps: int, beta: float = 0.35, offset: float = 0.0) -> np.ndarray:
+    """Root-raised-cosine taps (GLUE: absent from the reference), unit energy, sampled `offset`
+    samples late: a TX shaped with them is the nominal TX delayed by `offset` samples."""
     out = np.zeros(int(ntaps), dtype=np.float32)
-    _check(load_library().modem_rrc_taps(int(ntaps), int(sps), float(beta), _fptr(out)), "rrc_taps")
+    _check(load_library().modem_rrc_taps_offset(int(ntaps), int(sps), float(beta), float(offset), _fptr(out)), "rrc_taps")
     return out
 
 
@@ -890,6 +898,13 @@ class DemodulatorRx:
         k = prod.value
         return (None if oiq is None else (oiq if int(oiq.shape[0]) == k else oiq[:k])), \
                (None if osym is None else (osym if int(osym.shape[0]) == k else osym[:k]))
+
+    def timing(self, sps: int, block: int = 256, **kw) -> "TimingSync":
+        """The symbol timing synchronizer for this RX's output at `sps` samples per symbol, on the
+        RX's device and output dtype: the RX must run at sample rate (decim == 1)."""
+        if self.decim != 1:
+            raise ModemPanic(ERR_INVALID_ARG, "DemodulatorRx.timing: the RX must have decim == 1")
+        return TimingSync(sps, block=block, **{"in_dtype": self.out_dtype, "device": self.device, **kw})
 
     @staticmethod
     def process_batch(rxs, iqs, out_iq=None, out_sym=None, stream=None):
@@ -1484,6 +1499,78 @@ class CarrierSync:
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.modem_sync_destroy(self._h)
+            self._h = None
+
+
+# ------------------------------------------------------ symbol timing synchronizer ----
+class TimingSync:
+    """Feedforward symbol timing synchronizer (GLUE: the reference has none) at sample rate, on the
+    (n, 2) I/Q that `DemodulatorRx.process` returns with decim == 1 and in front of the carrier
+    synchronizer: block square-law delay estimates over `block` symbols of `sps` (4 or 8) samples,
+    unwrapped across blocks, applied as a piecewise-linear delay through a cubic interpolator
+    (include/modem_hip.h, "Symbol timing synchronizer"). The tracked delay stays within +-`span`
+    symbols and starts at `tau0` symbols; `flat` keeps one delay per block. Output symbol k is the
+    centre of the eye of grid symbol k - span.
+
+    `process(x)` returns (out, tau, quality) for the floor((carried + n) / (block sps)) blocks the
+    call completes: out (blocks * block, 2) of out_dtype, tau (blocks,) int64 the unwrapped delay of
+    each block in 2^-32 symbols, quality (blocks,) float32 |X| / S in [0, 1]; the samples of the
+    incomplete block carry into the next call. `flush()` returns the symbols of the incomplete
+    block. CUDA tensors (asynchronous on the current stream) or numpy arrays, results on the side
+    of the input."""
+
+    def __init__(self, sps: int, block: int = 256, span: int = 2, tau0: float = 0.0, flat: bool = False,
+                 in_dtype: int = DTYPE_F32, out_dtype: int = DTYPE_F32, device: int = 0):
+        if not 0 <= int(sps) < 1 << 32 or not 0 <= int(block) < 1 << 32 or not 0 <= int(span) < 1 << 32:
+            raise ModemPanic(ERR_INVALID_ARG, "TimingSync: sps, block and span are uint32")
+        self.sps, self.block, self.span, self.tau0, self.flat = int(sps), int(block), int(span), float(tau0), bool(flat)
+        self.in_dtype, self.out_dtype, self.device = in_dtype, out_dtype, device
+        h = ctypes.c_void_p()
+        _check(load_library().modem_timing_create(self.sps, self.block, self.span, self.tau0, 1 if flat else 0,
+                                                  in_dtype, out_dtype, device, ctypes.byref(h)), "TimingSync")
+        self._h = h
+        self._ncarry = 0
+
+    def nblocks(self, n: int) -> int:
+        return (self._ncarry + int(n)) // (self.block * self.sps)
+
+    def process(self, x, out=None, stream=None):
+        n = _check_rx_input(x, self.in_dtype, "TimingSync.process")
+        nb = self.nblocks(n)
+        np_dtype = _LLR_DTYPE[self.out_dtype]
+        y = out if out is not None else _empty_like_input(x, (nb * self.block, 2), np_dtype)
+        cap = _check_out(y, np_dtype, "TimingSync.process: out") // 2
+        if _is_torch(x):
+            import torch
+            tau = torch.empty(nb, dtype=torch.int64, device=x.device)
+            q = torch.empty(nb, dtype=torch.float32, device=x.device)
+        else:
+            tau, q = np.empty(nb, np.int64), np.empty(nb, np.float32)
+        prod, blocks = ctypes.c_size_t(), ctypes.c_size_t()
+        _check(load_library().modem_timing_process(self._h, _ptr(x) if n else None, n, _ptr(y), cap, _ptr(tau), _ptr(q),
+                                                   nb, ctypes.byref(prod), ctypes.byref(blocks),
+                                                   _stream_handle(stream, self.device)), "TimingSync.process")
+        self._ncarry = (self._ncarry + n) % (self.block * self.sps)
+        p = prod.value
+        return (y if int(y.shape[0]) == p else y[:p]), tau, q
+
+    def flush(self, like=None, stream=None):
+        n = self._ncarry // self.sps
+        ref = like if like is not None else np.zeros(1, np.float32)
+        y = _empty_like_input(ref, (n, 2), _LLR_DTYPE[self.out_dtype])
+        prod = ctypes.c_size_t()
+        _check(load_library().modem_timing_flush(self._h, _ptr(y), n, ctypes.byref(prod),
+                                                 _stream_handle(stream, self.device)), "TimingSync.flush")
+        self._ncarry = 0
+        return y
+
+    @property
+    def sample(self) -> int:
+        return int(load_library().modem_timing_sample(self._h))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.modem_timing_destroy(self._h)
             self._h = None
 
 

@@ -289,6 +289,38 @@ constexpr int kSyncState = 3;    // u64 words per state slot
 hipError_t launch_sync(const SyncParams& p, int in_dtype, int out_dtype, hipStream_t s);
 // flush: the ncarry carried symbols, rotated on the last block's line extended (i -> i + B)
 hipError_t launch_sync_flush(const SyncParams& p, int in_dtype, int out_dtype, hipStream_t s);
+// Symbol timing synchronizer (modem_timing.hip), one modem_timing_process call, passed by value. The
+// logical stream of the call is `pre || in`: the npre = H + carried samples the handle kept (H =
+// 2 span N + 1 samples of history before the current block, always present, zeros at the start of
+// a stream; then the samples of the incomplete block), then the n new ones. Block b of the call is
+// the B N samples from index H + b B N; its taps reach back to index b B N. The first nblk blocks
+// are estimated (phi, q), unwrapped (th) and interpolated (out); the last H + left samples of the
+// logical stream go to pre_new. state / state_new: {D, Phi, d} of the last block before / after
+// the call, as int64 (d = D_b - D_{b-1} as the apply step uses it: 0 for the stream's first block).
+// th has nblk + 1 entries: th[0] = D before the call, th[1 + b] = D of the call's block b.
+struct TimingParams {
+    const void* in;          // n interleaved (i, q) samples of the input dtype
+    const void* pre;         // npre samples of the input dtype, 16-byte aligned
+    void* pre_new;           // the other slot
+    void* out;               // nblk * B interleaved (i, q) of the output dtype
+    uint32_t* phi;           // [nblk]     workspace: Phi of every block
+    int64_t* th;             // [nblk + 1] workspace
+    float* q;                // [nblk]     workspace: quality of every block
+    const int64_t* state;
+    int64_t* state_new;
+    int64_t n, nblk;
+    int32_t npre;            // H + carried
+    int32_t lb, ln, span;    // log2 B, log2 N, span in symbols
+    int32_t first;           // no block was completed before this call: d of block 0 is 0
+    int32_t flat;            // MODEM_TIMING_FLAT: s = 0
+    int32_t nflush;          // flush: symbols to emit
+    int32_t in_align, out_align;   // set by the launcher: 2 = wide accesses aligned, 1 = sample-aligned, 0 = element-aligned
+};
+constexpr int kTimingState = 3;  // int64 words per state slot
+// est + scan + apply (nblk > 0), or only the move of the logical stream's tail into pre_new (nblk == 0)
+hipError_t launch_timing(const TimingParams& p, int in_dtype, int out_dtype, hipStream_t s);
+// flush: nflush symbols on the last block's line extended (i -> i + B); pre_new gets H zero samples
+hipError_t launch_timing_flush(const TimingParams& p, int in_dtype, int out_dtype, hipStream_t s);
 hipError_t launch_phases(float w, uint64_t s0, size_t n, float* out, hipStream_t s);
 hipError_t launch_prng_bits(uint64_t seed, uint8_t* out, size_t nbits, hipStream_t s);
 
