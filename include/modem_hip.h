@@ -676,6 +676,87 @@ modem_status modem_timing_flush(modem_timing* h, void* out, size_t cap, size_t* 
 uint64_t modem_timing_sample(const modem_timing* h);
 modem_status modem_timing_destroy(modem_timing* h);
 
+/* ---- Frame synchronizer (GLUE: the reference has none) -------------------------------------- */
+/* A data-aided frame synchronizer at symbol rate, on the symbols that modem_sync_process writes and
+ * in front of modem_demap_process or a slicer: a known unique word (UW) in front of each frame is
+ * correlated against the stream, the peaks of the normalised correlation are the frame starts, and
+ * the angle of each peak is the rotation the carrier synchronizer left (its M-fold ambiguity).
+ * modem_frame_gather cuts the frames out and takes that rotation off. The chain is
+ * rx -> [timing ->] carrier synchronizer -> frame synchronizer -> gather -> demapper, and needs no
+ * knowledge of the channel.
+ *
+ * Parameters: u[0..L-1], the unique word, interleaved f32 (re, im), 8 <= L <= 256, all values
+ * finite, Eu = sum |u[j]|^2 > 0 (summed in double, j ascending); guard = W, the half-width of the
+ * peak window, 1 <= W <= 256; threshold = thr, a finite double in (0, 1]; in_dtype F32 or F16
+ * (widened exactly). t2 = (float)(thr * thr * Eu) and the f32 (float)Eu are formed once at create.
+ *
+ * r[k] are the stream's symbols, k counted from the handle's first input symbol and never reset;
+ * modem_frame_symbol returns the number of symbols taken so far.
+ *
+ * 1. Correlation and energy, in f32, for every k whose L symbols exist (inside the current window,
+ *    step 5):  c[k] = sum_j r[k+j] * conj(u[j]),  e[k] = sum_j |r[k+j]|^2. The summation order
+ *    depends on j alone: four accumulators (cr, ci, e), indexed by j mod 4, start at 0 and take
+ *    their terms with j ascending, term j as
+ *      cr = fma(r.re, u.re, cr); cr = fma(r.im, u.im, cr);
+ *      ci = fma(r.im, u.re, ci); ci = fma(-r.re, u.im, ci);
+ *      e  = fma(r.re, r.re, e);  e  = fma(r.im, r.im, e);
+ *    and are joined as (a0 + a1) + (a2 + a3).  m[k] = fma(c.re, c.re, c.im * c.im).
+ * 2. Candidates: pass[k] iff m[k] and e[k] are finite, m[k] > 0 and m[k] >= t2 * e[k] (the product
+ *    rounded to f32): the normalised correlation |c| / sqrt(e Eu) >= thr, invariant to gain and to
+ *    any constant phase.
+ * 3. Peak picking: k is a hit iff pass[k], m[k] > m[k'] for every existing k' in k-W .. k-1 and
+ *    m[k] >= m[k'] for every existing k' in k+1 .. k+W. Positions before the window's first symbol,
+ *    and positions without all L symbols at a flush, do not exist and impose no condition; a
+ *    non-finite m[k'] imposes none either. So among equal maxima the earliest wins, and two hits
+ *    are always more than W apart.
+ * 4. Per hit, in ascending k: pos (uint64_t) = k of the UW's first symbol; phi (uint32_t) =
+ *    turn(c.im, c.re), the 32-bit turn fraction of the carrier synchronizer (within 2^-22 turns);
+ *    metric (float) = sqrt(m / (e * (float)Eu)), division and square root correctly rounded.
+ *    *count (uint64_t) = the number of hits decided in this call, never capped; only the first
+ *    min(*count, cap) hits are stored and nothing past them is written, so a small cap loses hits
+ *    but refuses nothing and changes no state differently.
+ * 5. Streaming: position k is decided once r up to k + W + L - 1 is known. The handle carries the
+ *    last 2W + L - 1 symbols on the device, in two slots: a call reads one and writes the other.
+ *    Any cut of a stream into calls, nsym == 0 included, yields the same concatenated hits.
+ *    modem_frame_flush decides the remaining positions that have all L symbols and drops the
+ *    carry: the next symbol starts a fresh window (no position before it exists), the counter k
+ *    goes on.
+ * 6. Limits: the correlation is coherent over L symbols, so a residual frequency offset must
+ *    satisfy |cfo per symbol| * L << 1: the stage belongs after the carrier synchronizer. The
+ *    rotation is meaningful only if the UW is not mapped onto itself by a rotation of 1/M turn,
+ *    which a nonzero sequence never is. */
+typedef struct modem_frame modem_frame;
+/* Bad len, guard, threshold, dtype, a non-finite or all-zero UW, a NULL uw or out: INVALID_ARG,
+ * before any device is looked at. The handle owns device memory: a bad ordinal is NO_DEVICE here. */
+modem_status modem_frame_create(const float* uw, uint32_t len, uint32_t guard, double threshold, int32_t in_dtype,
+                                int device, modem_frame** out);
+/* iq: nsym interleaved (i,q) of in_dtype; pos, phi, metric: cap entries each, phi and metric may be
+ * NULL; a NULL pos or count is INVALID_ARG. Device or host pointers, as modem_demap_process (host
+ * outputs make the call synchronous). */
+modem_status modem_frame_process(modem_frame* h, const void* iq, size_t nsym, uint64_t* pos, uint32_t* phi,
+                                 float* metric, size_t cap, uint64_t* count, void* stream);
+modem_status modem_frame_flush(modem_frame* h, uint64_t* pos, uint32_t* phi, float* metric, size_t cap,
+                               uint64_t* count, void* stream);
+/* The number of input symbols taken so far (0 for NULL). */
+uint64_t modem_frame_symbol(const modem_frame* h);
+modem_status modem_frame_destroy(modem_frame* h);
+/* Hits into frames the demapper can take; stateless. iq: nsym symbols of in_dtype, iq[0] being
+ * stream symbol `base`; pos, phi: cap entries as modem_frame_process wrote them, *count its count
+ * (all three read on the device, no read-back; phi NULL: no rotation); out: cap rows of len symbols
+ * of out_dtype; ok: cap bytes. power = M in {1, 2, 4, 8}, lm = log2 M; rot_f = 0 for M = 1, else
+ *   rot_f = ((uint32_t)(phi_f + (1u << (31 - lm)))) >> (32 - lm)
+ * the multiple of 1/M turn nearest phi_f, wrapping. For each row f < cap: if f < min(*count, cap)
+ * and the symbols pos_f + skip .. pos_f + skip + len - 1 all lie in [base, base + nsym), then
+ *   out[f][i] = r[pos_f - base + skip + i] * e^{-j 2 pi rot_f / M}   and ok[f] = 1,
+ * else the row is all zeros and ok[f] = 0. A rotation by a multiple of a quarter turn is done by
+ * swaps and sign changes (exact); the odd eighths of M = 8 multiply in f32 by (c, s) =
+ * cos, sin(2 pi rot_f / 8) as the channel model forms them: (fma(im, s, re * c), fma(-re, s, im * c)).
+ * F16 input is widened exactly, F16 output rounded to nearest even. Bad power, dtypes, len == 0 or a
+ * NULL count (or, with cap > 0, pos, out or ok): INVALID_ARG, before any device is looked at. */
+modem_status modem_frame_gather(const void* iq, size_t nsym, uint64_t base, const uint64_t* pos, const uint32_t* phi,
+                                const uint64_t* count, size_t cap, uint32_t skip, uint32_t len, uint32_t power,
+                                int32_t in_dtype, int32_t out_dtype, void* out, uint8_t* ok, int device, void* stream);
+
 /* ---- synthetic input (GLUE): splitmix64 bit stream, one byte per bit ------------------- */
 /* bit i = (word[i/64] >> (i%64)) & 1, word j = splitmix64 output j+1 from `seed`.
  * `out` must be a device pointer. */

@@ -41,6 +41,7 @@ __all__ = [
     "Channel", "count_errors",
     "CarrierSync", "SYNC_FLAT",
     "TimingSync",
+    "FrameSync",
 ]
 
 PI32 = float(np.float32(math.pi))      # std::f32::consts::PI
@@ -203,6 +204,12 @@ def load_library():
         "modem_timing_flush": (st, [vp, vp, sz, c.POINTER(sz), vp]),
         "modem_timing_sample": (u64, [vp]),
         "modem_timing_destroy": (st, [vp]),
+        "modem_frame_create": (st, [fp, u32, u32, c.c_double, c.c_int32, c.c_int, c.POINTER(vp)]),
+        "modem_frame_process": (st, [vp, vp, sz, vp, vp, vp, sz, vp, vp]),
+        "modem_frame_flush": (st, [vp, vp, vp, vp, sz, vp, vp]),
+        "modem_frame_symbol": (u64, [vp]),
+        "modem_frame_destroy": (st, [vp]),
+        "modem_frame_gather": (st, [vp, sz, u64, vp, vp, vp, sz, u32, u32, u32, c.c_int32, c.c_int32, vp, vp, c.c_int, vp]),
         "modem_chain_create": (st, [vp, vp, vp, sz, vp, sz, vp, vp, sz, c.POINTER(vp)]),
         "modem_chain_run": (st, [vp, c.POINTER(sz), c.POINTER(sz), vp]),
         "modem_chain_fused": (c.c_int, [vp]),
@@ -356,6 +363,22 @@ class _Phasor:
         power, norm, ref = _sync_params(self.lut(), type(self).__name__)
         return CarrierSync(power, block, norm, ref, **kw)
 
+    def framer(self, uw_symbols, **kw) -> "FrameSync":
+        """FrameSync for a unique word of this constellation: u = lut[uw_symbols]; the gather's
+        `power` is the M of synchronizer() when the table has a line and 1 otherwise. Further
+        keywords go to FrameSync."""
+        lut = self.lut()
+        idx = np.asarray(uw_symbols, dtype=np.int64).reshape(-1)
+        if len(idx) and (idx.min() < 0 or idx.max() >= len(lut)):
+            raise ModemPanic(ERR_INVALID_ARG, f"{type(self).__name__}.framer: a symbol outside the table")
+        try:
+            power = _sync_params(lut, type(self).__name__)[0]
+        except ModemPanic:
+            power = 1
+        f = FrameSync(lut[idx], **kw)
+        f.power = power
+        return f
+
     def detector(self, *args, **kw):
         """The noncoherent detector of a phasor that carries state from symbol to symbol (DMPSK,
         MFSK, BFSK); every other phasor is received through slicer() / demapper()."""
@@ -455,6 +478,9 @@ class _SamplePhasor(_Phasor):
 
     def demapper(self, **kw):
         raise ModemError(ERR_UNSUPPORTED, f"{type(self).__name__}: no memoryless demapper")
+
+    def framer(self, *args, **kw):
+        raise ModemError(ERR_UNSUPPORTED, f"{type(self).__name__}: no symbol table, no frame synchronizer")
 
     def synchronizer(self, *args, **kw):
         raise ModemError(ERR_UNSUPPORTED, f"{type(self).__name__}: no table to derive a carrier synchronizer from")
@@ -1571,6 +1597,100 @@ class TimingSync:
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.modem_timing_destroy(self._h)
+            self._h = None
+
+
+# --------------------------------------------------------------- frame synchronizer ----
+class FrameSync:
+    """Data-aided frame synchronizer (GLUE: the reference has none) at symbol rate, on the (n, 2)
+    symbols that `CarrierSync.process` returns: the unique word `uw` ((L, 2) float32, 8 <= L <= 256)
+    is correlated against the stream, and the peaks of the normalised correlation |c| / sqrt(e Eu)
+    that reach `threshold` and dominate `guard` positions on either side (default L) are the hits
+    (include/modem_hip.h, "Frame synchronizer").
+
+    `process(x, cap=None)` returns (pos, phi, metric, count) for the positions the call decides:
+    `count` (1,) the number of hits, never capped; the first min(count, cap) entries of pos (stream
+    index of the unique word's first symbol; numpy uint64, or the same bits in a torch int64), phi
+    (the angle of the peak as a 32-bit fraction of a turn; numpy uint32 / torch int32 bits) and
+    metric (float32) are written, the rest is left as allocated. `cap` defaults to the most hits
+    the call can decide. `flush()` decides what is left and starts a fresh window. `gather(x, base,
+    pos, phi, count, ...)` cuts `length` symbols from `skip` after each hit out of x (whose first
+    symbol is stream index `base`) and takes the nearest multiple of 1 / `power` turn to phi off:
+    (frames (cap, length, 2), ok (cap,) uint8). CUDA tensors (asynchronous on the current stream,
+    nothing is read back) or numpy arrays, results on the side of the input."""
+
+    def __init__(self, uw, guard: Optional[int] = None, threshold: float = 0.6, in_dtype: int = DTYPE_F32,
+                 device: int = 0):
+        u = np.ascontiguousarray(np.asarray(uw, dtype=np.float32))
+        if u.ndim != 2 or u.shape[1] != 2:
+            raise ModemPanic(ERR_INVALID_ARG, "FrameSync: uw must be (L, 2)")
+        self.uw, self.length = u, int(u.shape[0])
+        self.guard = self.length if guard is None else int(guard)
+        if not 0 <= self.guard < 1 << 32:
+            raise ModemPanic(ERR_INVALID_ARG, "FrameSync: guard is uint32")
+        self.threshold, self.in_dtype, self.device, self.power = float(threshold), in_dtype, device, 1
+        h = ctypes.c_void_p()
+        _check(load_library().modem_frame_create(_fptr(u), self.length, self.guard, self.threshold, in_dtype, device,
+                                                 ctypes.byref(h)), "FrameSync")
+        self._h = h
+        self._ncarry = 0
+
+    def _outputs(self, like, cap: int):
+        if _is_torch(like):
+            import torch
+            dev = like.device
+            return (torch.empty(cap, dtype=torch.int64, device=dev), torch.empty(cap, dtype=torch.int32, device=dev),
+                    torch.empty(cap, dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.int64, device=dev))
+        return np.empty(cap, np.uint64), np.empty(cap, np.uint32), np.empty(cap, np.float32), np.empty(1, np.uint64)
+
+    def process(self, x, cap: Optional[int] = None, stream=None):
+        n = _check_rx_input(x, self.in_dtype, "FrameSync.process")
+        if cap is None:
+            cap = (self._ncarry + n) // (self.guard + 1) + 1
+        pos, phi, metric, count = self._outputs(x, int(cap))
+        _check(load_library().modem_frame_process(self._h, _ptr(x) if n else None, n, _ptr(pos), _ptr(phi), _ptr(metric),
+                                                  int(cap), _ptr(count), _stream_handle(stream, self.device)),
+               "FrameSync.process")
+        self._ncarry = min(self._ncarry + n, 2 * self.guard + self.length - 1)
+        return pos, phi, metric, count
+
+    def flush(self, like=None, cap: Optional[int] = None, stream=None):
+        if cap is None:
+            cap = self._ncarry // (self.guard + 1) + 1
+        pos, phi, metric, count = self._outputs(like if like is not None else np.zeros(1, np.float32), int(cap))
+        _check(load_library().modem_frame_flush(self._h, _ptr(pos), _ptr(phi), _ptr(metric), int(cap), _ptr(count),
+                                                _stream_handle(stream, self.device)), "FrameSync.flush")
+        self._ncarry = 0
+        return pos, phi, metric, count
+
+    def gather(self, x, base: int, pos, phi, count, skip: Optional[int] = None, length: int = 1,
+               power: Optional[int] = None, out_dtype: int = DTYPE_F32, stream=None):
+        n = _check_rx_input(x, self.in_dtype, "FrameSync.gather")
+        cap = int(pos.shape[0])
+        if phi is not None and int(phi.shape[0]) != cap:
+            raise ModemPanic(ERR_INVALID_ARG, "FrameSync.gather: pos and phi differ in size")
+        if not 0 <= int(base) < 1 << 64:
+            raise ModemPanic(ERR_INVALID_ARG, "FrameSync.gather: base is uint64")
+        skip = self.length if skip is None else int(skip)
+        power = self.power if power is None else int(power)
+        if not 0 <= skip < 1 << 32 or not 0 <= int(length) < 1 << 32 or not 0 <= power < 1 << 32:
+            raise ModemPanic(ERR_INVALID_ARG, "FrameSync.gather: skip, length and power are uint32")
+        np_dtype = _LLR_DTYPE[out_dtype]
+        frames = _empty_like_input(x, (cap, int(length), 2), np_dtype)
+        ok = _empty_like_input(x, (cap,), np.uint8)
+        _check(load_library().modem_frame_gather(_ptr(x) if n else None, n, int(base), _ptr(pos), _ptr(phi), _ptr(count),
+                                                 cap, skip, int(length), power, self.in_dtype, out_dtype,
+                                                 _ptr(frames), _ptr(ok), self.device,
+                                                 _stream_handle(stream, self.device)), "FrameSync.gather")
+        return frames, ok
+
+    @property
+    def symbol(self) -> int:
+        return int(load_library().modem_frame_symbol(self._h))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.modem_frame_destroy(self._h)
             self._h = None
 
 

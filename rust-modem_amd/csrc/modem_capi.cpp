@@ -2324,6 +2324,178 @@ uint64_t modem_timing_sample(const modem_timing* h) { return h ? h->n : 0; }
 
 modem_status modem_timing_destroy(modem_timing* h) { delete h; return MODEM_OK; }
 
+// ---------------------------------------------------------------- frame synchronizer ----
+// Host side: the sizes, the slot index and the counters; device side: the unique word and the last
+// min(T, 2W + L - 1) symbols of the window (two slots, the emit kernel fills the other one).
+struct modem_frame {
+    int device = 0;
+    int32_t in_dtype = 0;
+    int32_t L = 0, W = 0, maxh = 0;
+    float t2 = 0.f, eu = 0.f;
+    float* d_uw = nullptr;
+    char* d_carry = nullptr;
+    int ccur = 0;
+    uint32_t ncarry = 0;
+    uint64_t n = 0;              // input symbols taken so far
+    Stage in_stage, pos_stage, phi_stage, met_stage, count_stage, cnt_ws, off_ws, rec_ws;
+    size_t ssz() const { return in_dtype == MODEM_DTYPE_F16 ? 4 : 8; }
+    size_t keep_max() const { return (size_t)(2 * W + L - 1); }
+    size_t slot_bytes() const { return (keep_max() * ssz() + 15) / 16 * 16; }
+    ~modem_frame() {
+        DeviceGuard g(device);
+        if (d_uw) (void)hipFree(d_uw);
+        if (d_carry) (void)hipFree(d_carry);
+    }
+};
+
+modem_status modem_frame_create(const float* uw, uint32_t len, uint32_t guard, double threshold, int32_t in_dtype,
+                                int device, modem_frame** out) {
+    if (!out) return MODEM_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (!uw || len < 8 || len > (uint32_t)mk::kFrameMaxL || guard < 1 || guard > (uint32_t)mk::kFrameMaxW) return MODEM_ERR_INVALID_ARG;
+    if (!std::isfinite(threshold) || !(threshold > 0.0) || !(threshold <= 1.0)) return MODEM_ERR_INVALID_ARG;
+    if (!iq_dtype_ok(in_dtype)) return MODEM_ERR_INVALID_ARG;
+    double eu = 0.0;
+    for (uint32_t j = 0; j < len; ++j) {
+        if (!std::isfinite(uw[2 * j]) || !std::isfinite(uw[2 * j + 1])) return MODEM_ERR_INVALID_ARG;
+        eu += (double)uw[2 * j] * (double)uw[2 * j] + (double)uw[2 * j + 1] * (double)uw[2 * j + 1];
+    }
+    if (!(eu > 0.0) || !std::isfinite(eu)) return MODEM_ERR_INVALID_ARG;
+    if (!device_ok(device)) return MODEM_ERR_NO_DEVICE;
+    DeviceGuard g(device);
+    if (!g.ok) return MODEM_ERR_NO_DEVICE;
+    modem_frame* h = new (std::nothrow) modem_frame;
+    if (!h) return MODEM_ERR_ALLOC;
+    h->device = device;
+    h->in_dtype = in_dtype;
+    h->L = (int32_t)len;
+    h->W = (int32_t)guard;
+    h->maxh = (mk::kFrameTile + h->W) / (h->W + 1);
+    h->t2 = (float)(threshold * threshold * eu);
+    h->eu = (float)eu;
+    modem_status st;
+    if ((st = dalloc(&h->d_uw, 2 * (size_t)len)) || (st = dalloc(&h->d_carry, 2 * h->slot_bytes()))) { delete h; return st; }
+    if (hipMemcpy(h->d_uw, uw, 2 * (size_t)len * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError(); delete h; return MODEM_ERR_HIP;
+    }
+    *out = h;
+    return MODEM_OK;
+}
+
+static modem_status frame_run(modem_frame* h, const void* iq, size_t nsym, uint64_t* pos, uint32_t* phi, float* metric,
+                              size_t cap, uint64_t* count, void* stream, bool flush) {
+    if (!h || !pos || !count || (nsym && !iq)) return MODEM_ERR_INVALID_ARG;
+    if (nsym > SIZE_MAX / 32) return MODEM_ERR_INVALID_ARG;
+    const size_t isz = h->in_dtype == MODEM_DTYPE_F16 ? 2 : 4;
+    if (!device_ok(h->device)) return MODEM_ERR_NO_DEVICE;
+    if (noncoh_ptr_bad(iq, isz, h->device) || noncoh_ptr_bad(pos, 8, h->device) || noncoh_ptr_bad(phi, 4, h->device) ||
+        noncoh_ptr_bad(metric, 4, h->device) || noncoh_ptr_bad(count, 8, h->device)) return MODEM_ERR_INVALID_ARG;
+    DeviceGuard g(h->device);
+    if (!g.ok) return MODEM_ERR_NO_DEVICE;
+    NoncohIo io{h->device, (hipStream_t)stream};
+    modem_status st;
+    mk::FrameParams p{};
+    const int64_t nc = h->ncarry, nlog = nc + (int64_t)nsym, L = h->L, W = h->W;
+    p.d0 = std::max<int64_t>(0, nc - W - L + 1);
+    p.d1 = flush ? (nlog >= L ? nlog - L + 1 : 0) : std::max<int64_t>(0, nlog - W - L + 1);
+    if (p.d1 < p.d0) p.d1 = p.d0;
+    p.ntiles = (p.d1 - p.d0 + mk::kFrameTile - 1) / mk::kFrameTile;
+    p.keep = flush ? 0 : (int32_t)std::min<int64_t>(nlog, (int64_t)h->keep_max());
+    void *dpos, *dphi, *dmet, *dcount;
+    if ((st = io.in(h->in_stage, iq, nsym * 2 * isz, &p.in)) || (st = io.out(h->pos_stage, pos, cap * 8, &dpos)) ||
+        (st = io.out(h->phi_stage, phi, cap * 4, &dphi)) || (st = io.out(h->met_stage, metric, cap * 4, &dmet)) ||
+        (st = io.out(h->count_stage, count, 8, &dcount))) return st;
+    if ((st = h->cnt_ws.ensure((size_t)p.ntiles * sizeof(uint32_t))) || (st = h->off_ws.ensure((size_t)p.ntiles * sizeof(uint64_t))) ||
+        (st = h->rec_ws.ensure((size_t)p.ntiles * h->maxh * 4 * sizeof(float)))) return st;
+    p.carry = h->d_carry + (size_t)h->ccur * h->slot_bytes();
+    p.carry_new = h->d_carry + (size_t)(h->ccur ^ 1) * h->slot_bytes();
+    p.uw = h->d_uw;
+    p.cnt = static_cast<uint32_t*>(h->cnt_ws.p);
+    p.off = static_cast<uint64_t*>(h->off_ws.p);
+    p.rec = static_cast<float*>(h->rec_ws.p);
+    p.pos = static_cast<uint64_t*>(dpos);
+    p.phi = static_cast<uint32_t*>(dphi);
+    p.metric = static_cast<float*>(dmet);
+    p.count = static_cast<uint64_t*>(dcount);
+    p.n = (int64_t)nsym;
+    p.base = h->n - (uint64_t)nc;
+    p.cap = cap;
+    p.t2 = h->t2;
+    p.eu = h->eu;
+    p.ncarry = (int32_t)nc;
+    p.L = h->L;
+    p.W = h->W;
+    p.maxh = h->maxh;
+    HIP_TRY(mk::launch_frame(p, h->in_dtype, io.s));
+    h->ncarry = (uint32_t)p.keep;
+    if (!flush) h->ccur ^= 1;                                       // the emit kernel filled the other carry slot
+    h->n += nsym;
+    if (dcount != count || dpos != pos || dphi != phi || dmet != metric) {
+        // host outputs: the count first, then only the hits that were stored
+        uint64_t got = 0;
+        HIP_TRY(hipMemcpyAsync(&got, dcount, 8, hipMemcpyDeviceToHost, io.s));
+        HIP_TRY(hipStreamSynchronize(io.s));
+        if (dcount != count) *count = got;
+        const size_t nw = (size_t)std::min<uint64_t>(got, cap);
+        if ((st = io.back(pos, dpos, nw * 8)) || (st = io.back(phi, dphi, nw * 4)) || (st = io.back(metric, dmet, nw * 4))) return st;
+    }
+    return io.finish();
+}
+
+modem_status modem_frame_process(modem_frame* h, const void* iq, size_t nsym, uint64_t* pos, uint32_t* phi, float* metric,
+                                 size_t cap, uint64_t* count, void* stream) {
+    return frame_run(h, iq, nsym, pos, phi, metric, cap, count, stream, false);
+}
+
+modem_status modem_frame_flush(modem_frame* h, uint64_t* pos, uint32_t* phi, float* metric, size_t cap, uint64_t* count,
+                               void* stream) {
+    return frame_run(h, nullptr, 0, pos, phi, metric, cap, count, stream, true);
+}
+
+uint64_t modem_frame_symbol(const modem_frame* h) { return h ? h->n : 0; }
+
+modem_status modem_frame_destroy(modem_frame* h) { delete h; return MODEM_OK; }
+
+modem_status modem_frame_gather(const void* iq, size_t nsym, uint64_t base, const uint64_t* pos, const uint32_t* phi,
+                                const uint64_t* count, size_t cap, uint32_t skip, uint32_t len, uint32_t power,
+                                int32_t in_dtype, int32_t out_dtype, void* out, uint8_t* ok, int device, void* stream) {
+    if (power != 1 && power != 2 && power != 4 && power != 8) return MODEM_ERR_INVALID_ARG;
+    if (!iq_dtype_ok(in_dtype) || !iq_dtype_ok(out_dtype) || len == 0) return MODEM_ERR_INVALID_ARG;
+    if ((nsym && !iq) || !count || (cap && (!pos || !out || !ok))) return MODEM_ERR_INVALID_ARG;
+    if (nsym > SIZE_MAX / 32 || cap > SIZE_MAX / 32 / len) return MODEM_ERR_INVALID_ARG;
+    if (!device_ok(device)) return MODEM_ERR_NO_DEVICE;
+    const size_t isz = in_dtype == MODEM_DTYPE_F16 ? 2 : 4, osz = out_dtype == MODEM_DTYPE_F16 ? 2 : 4;
+    if (noncoh_ptr_bad(iq, isz, device) || noncoh_ptr_bad(pos, 8, device) || noncoh_ptr_bad(phi, 4, device) ||
+        noncoh_ptr_bad(count, 8, device) || noncoh_ptr_bad(out, osz, device) || noncoh_ptr_bad(ok, 1, device)) return MODEM_ERR_INVALID_ARG;
+    if (cap == 0) return MODEM_OK;
+    DeviceGuard g(device);
+    if (!g.ok) return MODEM_ERR_NO_DEVICE;
+    NoncohIo io{device, (hipStream_t)stream};
+    Stage s_in, s_pos, s_phi, s_count, s_out, s_ok;                // host memory: staged through buffers of this call, synchronous
+    modem_status st;
+    mk::FrameGatherParams p{};
+    const void *dpos, *dphi, *dcount;
+    void *dout, *dok;
+    const size_t out_bytes = cap * len * 2 * osz;
+    if ((st = io.in(s_in, iq, nsym * 2 * isz, &p.in)) || (st = io.in(s_pos, pos, cap * 8, &dpos)) ||
+        (st = io.in(s_phi, phi, cap * 4, &dphi)) || (st = io.in(s_count, count, 8, &dcount)) ||
+        (st = io.out(s_out, out, out_bytes, &dout)) || (st = io.out(s_ok, ok, cap, &dok))) return st;
+    p.out = dout;
+    p.ok = static_cast<uint8_t*>(dok);
+    p.pos = static_cast<const uint64_t*>(dpos);
+    p.phi = static_cast<const uint32_t*>(dphi);
+    p.count = static_cast<const uint64_t*>(dcount);
+    p.n = nsym;
+    p.base = base;
+    p.cap = cap;
+    p.skip = skip;
+    p.len = len;
+    p.lm = power == 1 ? 0 : power == 2 ? 1 : power == 4 ? 2 : 3;
+    HIP_TRY(mk::launch_frame_gather(p, in_dtype, out_dtype, io.s));
+    if ((st = io.back(out, dout, out_bytes)) || (st = io.back(ok, dok, cap))) return st;
+    return io.finish();
+}
+
 modem_status modem_count_errors(const uint8_t* a, const uint8_t* b, size_t n, uint64_t* counts, int device, void* stream) {
     if (!counts || (n && (!a || !b))) return MODEM_ERR_INVALID_ARG;
     if (!device_ok(device)) return MODEM_ERR_NO_DEVICE;

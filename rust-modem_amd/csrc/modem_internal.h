@@ -321,6 +321,52 @@ constexpr int kTimingState = 3;  // int64 words per state slot
 hipError_t launch_timing(const TimingParams& p, int in_dtype, int out_dtype, hipStream_t s);
 // flush: nflush symbols on the last block's line extended (i -> i + B); pre_new gets H zero samples
 hipError_t launch_timing_flush(const TimingParams& p, int in_dtype, int out_dtype, hipStream_t s);
+// Frame synchronizer (modem_frame.hip), one modem_frame_process or modem_frame_flush call, passed by
+// value. The logical stream of the call is `carry || in`: ncarry symbols the handle kept (the last
+// min(T, 2W + L - 1) of its window), then the n new ones, nlog = ncarry + n in all; logical
+// position 0 is stream symbol `base`. Positions 0 .. nlog - L exist; d0 .. d1 - 1 are decided by
+// this call (tile t covers d0 + 256 t ..). cnt / off: hits per tile and their exclusive prefix sum;
+// rec: maxh records {c.re, c.im, e, offset in the tile} per tile, maxh = ceil(256 / (W + 1)) (hits
+// are more than W apart). The emit step writes the first min(*count, cap) hits and moves the last
+// `keep` logical symbols into carry_new.
+struct FrameParams {
+    const void* in;          // n interleaved (i, q) of the input dtype
+    const void* carry;       // ncarry symbols of the input dtype, 16-byte aligned
+    void* carry_new;         // the other carry slot
+    const float* uw;         // L (re, im) pairs
+    uint32_t* cnt;           // [ntiles] workspace
+    uint64_t* off;           // [ntiles] workspace
+    float* rec;              // [ntiles * maxh * 4] workspace
+    uint64_t* pos;           // [cap]
+    uint32_t* phi;           // [cap] or NULL
+    float* metric;           // [cap] or NULL
+    uint64_t* count;
+    int64_t n, d0, d1, ntiles;
+    uint64_t base, cap;
+    float t2, eu;
+    int32_t ncarry, L, W, maxh, keep;
+    int32_t in_align;        // set by the launcher: 1 = symbol-aligned, 0 = element-aligned
+};
+constexpr int kFrameTile = 256;  // decided positions per workgroup
+constexpr int kFrameMaxL = 256, kFrameMaxW = 256;
+// correlate + pick (ntiles > 0), scan (always: it writes *count), emit + carry
+hipError_t launch_frame(const FrameParams& p, int in_dtype, hipStream_t s);
+// Frame gather (modem_frame.hip): row f < cap of `out` = len symbols from in[pos[f] - base + skip],
+// rotated by the multiple of 1 / M turn nearest phi[f] (M = 2^lm; phi NULL or lm 0: none), or zeros
+// and ok[f] = 0 when f >= min(*count, cap) or the symbols are not all inside [base, base + n).
+struct FrameGatherParams {
+    const void* in;
+    void* out;
+    uint8_t* ok;
+    const uint64_t* pos;
+    const uint32_t* phi;
+    const uint64_t* count;
+    uint64_t n, base, cap;
+    uint32_t skip, len;
+    int32_t lm;
+    int32_t in_elem, out_elem;   // set by the launcher: the buffer is only element-aligned
+};
+hipError_t launch_frame_gather(const FrameGatherParams& p, int in_dtype, int out_dtype, hipStream_t s);
 hipError_t launch_phases(float w, uint64_t s0, size_t n, float* out, hipStream_t s);
 hipError_t launch_prng_bits(uint64_t seed, uint8_t* out, size_t nbits, hipStream_t s);
 
