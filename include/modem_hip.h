@@ -757,6 +757,75 @@ modem_status modem_frame_gather(const void* iq, size_t nsym, uint64_t base, cons
                                 const uint64_t* count, size_t cap, uint32_t skip, uint32_t len, uint32_t power,
                                 int32_t in_dtype, int32_t out_dtype, void* out, uint8_t* ok, int device, void* stream);
 
+/* ---- Convolutional code (GLUE: the reference has none) -------------------------------------- */
+/* A rate-1/n convolutional code: a stateless encoder in front of modem_tx_process and a batched
+ * soft-decision Viterbi decoder behind modem_demap_process, on the frames that modem_frame_gather
+ * cuts out. Frames are independent: each starts in state 0 and, with MODEM_CONV_TAIL, ends there.
+ * The chain is bits -> encode -> tx ... rx -> [timing ->] carrier synchronizer -> frame
+ * synchronizer -> gather -> demapper -> viterbi. Every metric is an integer, so the decoder's
+ * output is specified bit for bit.
+ *
+ * Parameters: the constraint length K, 3 <= K <= 9; n in {2, 3} generator polynomials g[j],
+ * 0 < g[j] < 2^K; S = 2^(K-1) states; flags: MODEM_CONV_TAIL. With the tail, K-1 zero bits follow
+ * the nbits information bits of a frame and T = nbits + K - 1 steps; without, T = nbits. A frame is
+ * n * T coded bits.
+ *
+ * 1. Encoder step t, with input bit b (0 in the tail) and state s (0 at the start of a frame):
+ *      reg = (b << (K-1)) | s;   coded bit j = parity(reg & g[j]), stored at index t*n + j;
+ *      the next state is reg >> 1.
+ *    The top bit of g taps the current bit, as in the usual octal notation: the customary K = 7
+ *    pair is (0171, 0133).
+ * 2. Decoder input: llr is rows of at least n * T values of in_dtype (F32, F16 or I8), row stride
+ *    `stride` in elements; a positive value means "bit 0", the demapper's sign. Each value is
+ *    quantised to an integer q before use:
+ *      I8:        q = max(v, -127)
+ *      F32, F16:  q = (int) rintf(fminf(fmaxf(v * qscale, -127.f), 127.f))
+ *    F16 widened exactly, the product one f32 multiply, ties to even; qscale finite and positive.
+ *    A NaN is unspecified (and memory-safe). q = 0 is an erasure: a caller depunctures by inserting
+ *    zeros.
+ * 3. Path metrics are int32 correlations, maximised: pm[0] = 0 at the start of a frame, every
+ *    other state -2^30. State s' at step t+1 has the input bit b = s' >> (K-2) and the two
+ *    predecessors p_x = ((s' << 1) & (S-1)) | x, x in {0, 1};
+ *      m_x = pm[p_x] + sum_j (1 - 2 c_j) q[t*n + j],  c_j coded bit j of reg = (b << (K-1)) | p_x.
+ *    The survivor is x = 1 iff m_1 > m_0 (ties keep x = 0); dec[t][s'] = x, pm'[s'] = m_x.
+ *    n * 127 * T < 2^29 under the length limit below: nothing overflows, and the start value never
+ *    wins.
+ * 4. Traceback: the end state is 0 with the tail, else the state of the largest final metric, the
+ *    lowest index among equals. Walking back from step T-1: bit_t = s' >> (K-2), the previous state
+ *    is p_x with x = dec[t][s']. The first nbits bits go to `out`, one byte per bit, rows of stride
+ *    out_stride; nothing is written past nbits in a row. metric[f] (int32, may be NULL) is the end
+ *    state's final metric.
+ * 5. ok may be NULL; otherwise nframes bytes as modem_frame_gather writes them: a row with
+ *    ok[f] == 0 is not decoded, its nbits output bytes and its metric are 0. Nothing is read back.
+ * 6. Limits: this version keeps the decision bits of a frame group in LDS, 32 KiB of them:
+ *    T <= 4096 for S <= 64, 2048 for S = 128, 1024 for S = 256. Longer frames, and nbits == 0, are
+ *    INVALID_ARG. Streaming and sliding-window decoding of an unterminated stream are out of scope.
+ *
+ * Every buffer (bits, out, llr, ok, metric) is device memory of the entry's device; anything else
+ * is INVALID_ARG. The calls are asynchronous on `stream`. */
+#define MODEM_CONV_TAIL 1u        /* K-1 zero bits end each frame in state 0 */
+/* bits: nframes rows of nbits bytes, row stride in_stride >= nbits, only bit 0 of a byte is used;
+ * out: rows of n * T bytes (the TX's one-byte-per-bit input), row stride out_stride >= n * T; bytes
+ * past n * T in a row are not written. Bad K, n, polynomial, flags, nbits == 0, a stride too small
+ * or (with nframes > 0) a NULL pointer: INVALID_ARG, before any device is looked at; then a bad
+ * ordinal is NO_DEVICE; nframes == 0 succeeds and writes nothing. */
+modem_status modem_conv_encode(uint32_t K, const uint32_t* polys, uint32_t n, uint32_t flags, const uint8_t* bits,
+                               size_t nframes, size_t nbits, size_t in_stride, uint8_t* out, size_t out_stride, int device,
+                               void* stream);
+typedef struct modem_viterbi modem_viterbi;
+/* Bad K, n, polynomial, flags, dtype or a NULL polys or out: INVALID_ARG, before any device is
+ * looked at. The handle holds the code's branch table on the device and no stream state: a bad
+ * ordinal is NO_DEVICE here. */
+modem_status modem_viterbi_create(uint32_t K, const uint32_t* polys, uint32_t n, uint32_t flags, int32_t in_dtype, int device,
+                                  modem_viterbi** out);
+/* A NULL handle, nbits == 0 or a frame over the limit, stride < n * T, out_stride < nbits, a qscale
+ * that is not finite and positive (checked for I8 too, where it is unused), or (with nframes > 0) a
+ * NULL llr or out: INVALID_ARG, before any device is looked at, and nothing is written.
+ * nframes == 0 succeeds and writes nothing. */
+modem_status modem_viterbi_process(modem_viterbi* h, const void* llr, size_t stride, size_t nframes, size_t nbits, float qscale,
+                                   const uint8_t* ok, uint8_t* out, size_t out_stride, int32_t* metric, void* stream);
+modem_status modem_viterbi_destroy(modem_viterbi* h);
+
 /* ---- synthetic input (GLUE): splitmix64 bit stream, one byte per bit ------------------- */
 /* bit i = (word[i/64] >> (i%64)) & 1, word j = splitmix64 output j+1 from `seed`.
  * `out` must be a device pointer. */

@@ -42,6 +42,7 @@ __all__ = [
     "CarrierSync", "SYNC_FLAT",
     "TimingSync",
     "FrameSync",
+    "ConvCode", "ViterbiDecoder", "CONV_TAIL",
 ]
 
 PI32 = float(np.float32(math.pi))      # std::f32::consts::PI
@@ -52,6 +53,7 @@ DTYPE_F32, DTYPE_F16, DTYPE_I16 = 0, 1, 2   # I16: real samples, RX input (demod
 DTYPE_I8 = 3                                # only as SoftDemapper's out_dtype
 DEMAP_AUTO, DEMAP_GENERAL = 0, 1
 SYNC_FLAT = 1                               # CarrierSync flags: one phase per block
+CONV_TAIL = 1                               # ConvCode flags: K-1 zero bits end each frame in state 0
 OUT_IQ_MIXED, OUT_IQ_BASEBAND, OUT_REAL = 0, 1, 2
 MIX_COMPLEX, MIX_REFERENCE_REAL, MIX_REFERENCE_REAL_EXACT = 0, 1, 2
 SLICER_NONE, SLICER_NEAREST, SLICER_QAM_AXIS = 0, 1, 2
@@ -210,6 +212,10 @@ def load_library():
         "modem_frame_symbol": (u64, [vp]),
         "modem_frame_destroy": (st, [vp]),
         "modem_frame_gather": (st, [vp, sz, u64, vp, vp, vp, sz, u32, u32, u32, c.c_int32, c.c_int32, vp, vp, c.c_int, vp]),
+        "modem_conv_encode": (st, [u32, c.POINTER(u32), u32, u32, vp, sz, sz, sz, vp, sz, c.c_int, vp]),
+        "modem_viterbi_create": (st, [u32, c.POINTER(u32), u32, u32, c.c_int32, c.c_int, c.POINTER(vp)]),
+        "modem_viterbi_process": (st, [vp, vp, sz, sz, sz, f32, vp, vp, sz, vp, vp]),
+        "modem_viterbi_destroy": (st, [vp]),
         "modem_chain_create": (st, [vp, vp, vp, sz, vp, sz, vp, vp, sz, c.POINTER(vp)]),
         "modem_chain_run": (st, [vp, c.POINTER(sz), c.POINTER(sz), vp]),
         "modem_chain_fused": (c.c_int, [vp]),
@@ -1691,6 +1697,114 @@ class FrameSync:
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.modem_frame_destroy(self._h)
+            self._h = None
+
+
+# ---------------------------------------------------------------- convolutional code ----
+class ConvCode:
+    """A rate-1/n convolutional code (GLUE: the reference has none; include/modem_hip.h,
+    "Convolutional code"): constraint length 3 <= K <= 9, n = 2 or 3 generator polynomials whose top
+    bit taps the current input bit (the usual octal notation; the default is the customary K = 7
+    pair), and with `tail` K-1 zero bits that end every frame in state 0.
+
+    `encode(bits)` takes (nframes, nbits) uint8 on the device, one bit per byte (only bit 0 counts),
+    and returns the (nframes, n T) coded bits, T = nbits + K - 1 with the tail, as
+    `DigitalModulator.process` takes them once flattened. `coded_bits(nbits)` is n T.
+    `decoder(in_dtype)` is the `ViterbiDecoder` of the code."""
+
+    def __init__(self, K: int = 7, polys: Sequence[int] = (0o171, 0o133), tail: bool = True):
+        self.K, self.polys, self.tail = int(K), tuple(int(g) for g in polys), bool(tail)
+        self.n = len(self.polys)
+        if not 3 <= self.K <= 9 or self.n not in (2, 3) or any(not 0 < g < 1 << self.K for g in self.polys):
+            raise ModemPanic(ERR_INVALID_ARG, f"ConvCode: K = {K}, polys = {polys}")
+        self.flags = CONV_TAIL if self.tail else 0
+
+    def _polys(self):
+        return (ctypes.c_uint32 * self.n)(*self.polys)
+
+    def steps(self, nbits: int) -> int:
+        return int(nbits) + (self.K - 1 if self.tail else 0)
+
+    def coded_bits(self, nbits: int) -> int:
+        return self.n * self.steps(nbits)
+
+    def encode(self, bits, out=None, stream=None):
+        if not _is_torch(bits) or not bits.is_cuda or bits.dim() != 2 or _dtype_name(bits) != "uint8":
+            raise ValueError("ConvCode.encode: bits must be a 2-D uint8 CUDA tensor")
+        import torch
+        nframes, nbits = int(bits.shape[0]), int(bits.shape[1])
+        ncoded = self.coded_bits(nbits)
+        if out is None:
+            out = torch.empty((nframes, ncoded), dtype=torch.uint8, device=bits.device)
+        elif _dtype_name(out) != "uint8" or out.dim() != 2 or int(out.shape[0]) != nframes or int(out.shape[1]) < ncoded:
+            raise ValueError(f"ConvCode.encode: out must be uint8 ({nframes}, >= {ncoded})")
+        device = _device_of(bits, 0)
+        _check(load_library().modem_conv_encode(self.K, self._polys(), self.n, self.flags, _ptr(bits) if nframes else None,
+                                                nframes, nbits, nbits, _ptr(out) if nframes else None, int(out.shape[1]),
+                                                device, _stream_handle(stream, device)), "ConvCode.encode")
+        return out
+
+    def decoder(self, in_dtype: int = DTYPE_I8, device: int = 0) -> "ViterbiDecoder":
+        return ViterbiDecoder(self, in_dtype=in_dtype, device=device)
+
+
+class ViterbiDecoder:
+    """Batched soft-decision Viterbi decoder of a `ConvCode` on the demapper's LLRs (positive =
+    "bit 0"), int8 (the default), float16 or float32; float input is quantised to integers in
+    +-127 as rint(clamp(llr * qscale)). Metrics are integers: the output is specified bit for bit.
+
+    `process(llr, nbits, stride=None, ok=None, qscale=1.0, want_metric=True)` -> (bits, metric):
+    `llr` is a CUDA tensor: 2-D (nframes, >= n T), or of any shape with `stride` (elements between
+    frames), or frames of n T values back to back, so that the demapper's (nsym, bps) output over
+    `frames.view(-1, 2)` passes straight in; `ok` the (nframes,)
+    uint8 flags of `FrameSync.gather` or None: a frame with ok == 0 is not decoded, its bits and
+    metric are 0. bits is (nframes, nbits) uint8, metric (nframes,) int32 (the final correlation) or
+    None. Asynchronous on the current stream; nothing is read back. A frame may have at most 4096
+    steps (2048 for K = 8, 1024 for K = 9)."""
+
+    def __init__(self, code: ConvCode, in_dtype: int = DTYPE_I8, device: int = 0):
+        self.code, self.in_dtype, self.device = code, in_dtype, device
+        h = ctypes.c_void_p()
+        _check(load_library().modem_viterbi_create(code.K, code._polys(), code.n, code.flags, in_dtype, device,
+                                                   ctypes.byref(h)), "ViterbiDecoder")
+        self._h = h
+
+    def process(self, llr, nbits: int, stride: Optional[int] = None, ok=None, qscale: float = 1.0,
+                want_metric: bool = True, stream=None):
+        if not _is_torch(llr) or not llr.is_cuda:
+            raise ValueError("ViterbiDecoder.process: llr must be a CUDA tensor")
+        if _dtype_name(llr) != np.dtype(_LLR_DTYPE[self.in_dtype]).name:
+            raise ValueError(f"ViterbiDecoder.process: llr must be {np.dtype(_LLR_DTYPE[self.in_dtype]).name} "
+                             f"(the handle's in_dtype), got {_dtype_name(llr)}")
+        import torch
+        nbits = int(nbits)
+        ncoded = self.code.coded_bits(nbits)
+        total = int(llr.numel())
+        if stride is not None:
+            stride = int(stride)
+            if stride <= 0:
+                raise ValueError("ViterbiDecoder.process: stride must be positive")
+            nframes = 0 if total < ncoded else (total - ncoded) // stride + 1
+        elif llr.dim() == 2 and int(llr.shape[1]) >= ncoded:
+            nframes, stride = int(llr.shape[0]), int(llr.shape[1])
+        elif total % ncoded == 0:                          # frames back to back, e.g. the demapper's (nsym, bps)
+            nframes, stride = total // ncoded, ncoded
+        else:
+            raise ValueError(f"ViterbiDecoder.process: {total} values are not whole frames of {ncoded}; give a stride")
+        if ok is not None:
+            if not _is_torch(ok) or _dtype_name(ok) != "uint8" or int(ok.numel()) != nframes:
+                raise ValueError(f"ViterbiDecoder.process: ok must be {nframes} uint8 flags on the device")
+        bits = torch.empty((nframes, nbits), dtype=torch.uint8, device=llr.device)
+        metric = torch.empty((nframes,), dtype=torch.int32, device=llr.device) if want_metric else None
+        _check(load_library().modem_viterbi_process(self._h, _ptr(llr) if nframes else None, stride, nframes, nbits,
+                                                    float(qscale), _ptr(ok), _ptr(bits) if nframes else None, nbits,
+                                                    _ptr(metric), _stream_handle(stream, self.device)),
+               "ViterbiDecoder.process")
+        return bits, metric
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.modem_viterbi_destroy(self._h)
             self._h = None
 
 

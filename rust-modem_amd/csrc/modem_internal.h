@@ -367,6 +367,34 @@ struct FrameGatherParams {
     int32_t in_elem, out_elem;   // set by the launcher: the buffer is only element-aligned
 };
 hipError_t launch_frame_gather(const FrameGatherParams& p, int in_dtype, int out_dtype, hipStream_t s);
+// Convolutional code (modem_fec.hip), include/modem_hip.h "Convolutional code". The encoder: row f
+// of `bits` (nbits bytes, bit 0 of each) into row f of `out` (n * T bytes), T = nbits + K - 1 with
+// the tail, else nbits; g by value.
+struct ConvEncodeParams {
+    const uint8_t* bits;
+    uint8_t* out;
+    uint64_t nframes, nbits, T, in_stride, out_stride;
+    uint32_t g[3];
+    int32_t K, n;
+};
+hipError_t launch_conv_encode(const ConvEncodeParams& p, hipStream_t s);
+// The Viterbi decoder, one modem_viterbi_process call, passed by value. table: the S branch words
+// of the code (modem_fec_math.h, fec_branch_word), the handle's only device memory. llr: nframes rows
+// of n * T values, row stride `stride` elements; out: rows of nbits bytes; ok, metric: NULL or
+// nframes entries. A wave decodes 64 / S frames (S <= 64) or one frame with S / 64 states per lane.
+struct ViterbiParams {
+    const void* llr;
+    const uint8_t* ok;
+    const uint32_t* table;
+    uint8_t* out;
+    int32_t* metric;
+    uint64_t nframes, stride, out_stride;
+    float qscale;
+    int32_t K, n, tail;
+    int32_t nbits, T;
+};
+// in_dtype: 0 F32, 1 F16, 3 I8
+hipError_t launch_viterbi(const ViterbiParams& p, int in_dtype, hipStream_t s);
 hipError_t launch_phases(float w, uint64_t s0, size_t n, float* out, hipStream_t s);
 hipError_t launch_prng_bits(uint64_t seed, uint8_t* out, size_t nbits, hipStream_t s);
 
