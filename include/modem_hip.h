@@ -41,6 +41,21 @@
  *   - Streaming: consecutive `*_process` calls equal one long call (the handle carries the
  *     carrier sample counter, the FIR history, leftover bits and the decimation phase);
  *     `*_flush` drains the filter with zeros.
+ *   - Streams: a call whose buffers are all device memory queues everything it does (kernels,
+ *     copies) on `stream` alone, in order, returns without waiting for the device and reads
+ *     nothing back (tests/test_gpu_streams.py). The calls that wait for `stream` are those
+ *     with a host pointer among their buffers, modem_tx_scan_states, and modem_count_errors on
+ *     host memory; `*_create` copies tables with blocking copies and `*_destroy` frees device
+ *     memory, which waits for the whole device: destroy a handle once its stream has drained.
+ *     One handle, one stream at a time: a call reads the device state the previous call of
+ *     that handle wrote, so consecutive calls go to one stream, or the caller orders the two
+ *     streams with an event. Distinct handles share no device state and may run on distinct
+ *     streams at once. Workspaces whose size follows the call (the per-symbol states of a
+ *     DMPSK / MFSK / BFSK modem_tx, the per-block estimates of modem_sync and modem_timing,
+ *     the per-tile tables of modem_frame) are allocated by the first call that needs them and
+ *     grown, at least doubling, by a larger one; growing allocates and never frees: an
+ *     outgrown buffer, which queued kernels may still use, lives until the handle is
+ *     destroyed (all of them together are smaller than the live one).
  *   - One handle = one device; a handle is not thread-safe (it mirrors `&mut self`);
  *     distinct handles may be driven from different host threads. Device buffers passed to
  *     a handle must live on that handle's device (another GPU's memory: INVALID_ARG).

@@ -1812,7 +1812,8 @@ def count_errors(a, b, counts=None, stream=None, device: int = 0):
     """counts[0] += #{i: a[i] != b[i]}, counts[1] += sum_i popcount(a[i] ^ b[i]) over two uint8
     buffers of one size (bits, one byte each, or symbols), both CUDA tensors (asynchronous on the
     current stream; no host copy) or both numpy arrays. `counts`: a 2-element int64 tensor / array
-    on the same side to accumulate into, or None for a zeroed one. Returns it."""
+    on the same side to accumulate into, or None for a new one, zeroed on the stream of the call
+    (`stream`, else the current one). Returns it."""
     if _is_torch(a) != _is_torch(b) or (counts is not None and _is_torch(counts) != _is_torch(a)):
         raise ModemPanic(ERR_INVALID_ARG, "count_errors: a, b and counts must be on one side")
     n = _check_out(a, np.uint8, "count_errors: a")
@@ -1821,7 +1822,14 @@ def count_errors(a, b, counts=None, stream=None, device: int = 0):
     if counts is None:
         if _is_torch(a):
             import torch
-            counts = torch.zeros(2, dtype=torch.int64, device=a.device)
+            if stream is None:
+                counts = torch.zeros(2, dtype=torch.int64, device=a.device)
+            else:
+                # the zero-fill must be ordered before the kernel: queue it on the kernel's stream,
+                # not on torch's current one
+                s = stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(int(stream), device=a.device)
+                with torch.cuda.stream(s):
+                    counts = torch.zeros(2, dtype=torch.int64, device=a.device)
         else:
             counts = np.zeros(2, dtype=np.int64)
     elif _check_out(counts, np.int64, "count_errors: counts") != 2:

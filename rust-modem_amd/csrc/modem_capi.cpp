@@ -101,6 +101,31 @@ struct Stage {
     ~Stage() { if (p) (void)hipFree(p); }
 };
 
+// Growable device workspace of a handle's device-only path (include/modem_hip.h, "Streams").
+// Growing never frees: hipFree waits for the whole device, which a call documented as asynchronous
+// must not do, and kernels already queued may still use the old buffer. A buffer that was outgrown
+// is retired and lives until the handle is destroyed; the capacity at least doubles each time, so
+// the retired buffers together stay below the live one.
+struct Workspace {
+    void* p = nullptr;
+    size_t cap = 0;
+    std::vector<void*> retired;
+    modem_status ensure(size_t bytes) {
+        if (bytes <= cap) return MODEM_OK;
+        const size_t want = std::max(bytes, 2 * cap);
+        void* q = nullptr;
+        if (hipMalloc(&q, want) != hipSuccess) { (void)hipGetLastError(); return MODEM_ERR_ALLOC; }
+        if (p) retired.push_back(p);
+        p = q;
+        cap = want;
+        return MODEM_OK;
+    }
+    ~Workspace() {
+        if (p) (void)hipFree(p);
+        for (void* r : retired) (void)hipFree(r);
+    }
+};
+
 bool device_ok(int device) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return false; }
@@ -352,10 +377,10 @@ struct modem_tx {
     int ph_kind = 0;                // sample-dependent phasor (tx_phasor), else 0
     float ph_amp = 0.f, ph_freq = 0.f, ph_shift = 0.f, ph_max = 0.f;
     int ph_spb = 0, ph_map = 0;
-    Stage scan_stage;               // per-symbol states of the scanned phasors
+    Workspace scan_stage;           // per-symbol states of the scanned phasors
     size_t scan_n = 0;              // symbols of the last call, in scan_stage (modem_tx_scan_states)
     int scan_path = 0;              // how the last call scanned them (modem_tx_scan_path)
-    Stage batch_params;             // a scan batch's parameter blocks, when this is its first handle
+    Workspace batch_params;         // a scan batch's parameter blocks, when this is its first handle
     float2* d_hist[2] = {nullptr, nullptr};
     uint8_t* d_carry[2] = {nullptr, nullptr};
     int hcur = 0, ccur = 0, ncarry = 0;
@@ -652,6 +677,7 @@ static modem_status tx_launch(modem_tx* h, const uint8_t* dbits, size_t nbits, b
     p.scan = nullptr;
     if (phasor_scanned(h->ph_kind)) {
         h->scan_n = 0;                  // the stage is rewritten (or regrown): no states until this call is queued
+        // (regrown without a free: the previous call's kernels may still be queued on its buffer)
         if ((st = h->scan_stage.ensure((size_t)std::max<int64_t>(nsym, 1) * sizeof(float2)))) return st;
         p.scan = static_cast<float2*>(h->scan_stage.p);
     }
@@ -2020,7 +2046,8 @@ struct modem_sync {
     uint32_t ncarry = 0;
     bool first = true;           // no block completed yet
     uint64_t n = 0;              // input symbols taken so far
-    Stage in_stage, out_stage, phi_ws, th_ws, q_ws;
+    Stage in_stage, out_stage;
+    Workspace phi_ws, th_ws, q_ws;
     size_t ssz() const { return in_dtype == MODEM_DTYPE_F16 ? 4 : 8; }
     size_t slot_bytes() const { return ((size_t)1 << lb) * ssz(); }
     ~modem_sync() {
@@ -2178,7 +2205,8 @@ struct modem_timing {
     uint32_t ncarry = 0;         // samples of the incomplete block
     bool first = true;           // no block completed yet
     uint64_t n = 0;              // input samples taken so far
-    Stage in_stage, out_stage, phi_ws, th_ws, q_ws;
+    Stage in_stage, out_stage;
+    Workspace phi_ws, th_ws, q_ws;
     size_t ssz() const { return in_dtype == MODEM_DTYPE_F16 ? 4 : 8; }
     size_t hist() const { return 2 * (size_t)span * ((size_t)1 << ln) + 1; }
     size_t bn() const { return (size_t)1 << (lb + ln); }
@@ -2338,7 +2366,8 @@ struct modem_frame {
     int ccur = 0;
     uint32_t ncarry = 0;
     uint64_t n = 0;              // input symbols taken so far
-    Stage in_stage, pos_stage, phi_stage, met_stage, count_stage, cnt_ws, off_ws, rec_ws;
+    Stage in_stage, pos_stage, phi_stage, met_stage, count_stage;
+    Workspace cnt_ws, off_ws, rec_ws;
     size_t ssz() const { return in_dtype == MODEM_DTYPE_F16 ? 4 : 8; }
     size_t keep_max() const { return (size_t)(2 * W + L - 1); }
     size_t slot_bytes() const { return (keep_max() * ssz() + 15) / 16 * 16; }
