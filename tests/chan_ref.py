@@ -46,9 +46,19 @@ def rotate(step, phase0, n_index, n):
     return np.exp(2j * np.pi * (np.array(ph, dtype=np.float64) * 2.0 ** -53))
 
 
-def channel(x, gain=1.0, nco=(0, 0), n0=0.0, seed=0, s0=0):
+def rotate_np(step, phase0, n_index, n):
+    """rotate() in numpy uint64 wrap-around arithmetic, for millions of samples
+    (tests/test_chan_host.py holds it equal to rotate(), element for element)."""
+    with np.errstate(over="ignore"):
+        idx = np.arange(n, dtype=np.uint64) + np.uint64(int(n_index) & MASK)
+        ph = (np.uint64(int(phase0) & MASK) + np.uint64(int(step) & MASK) * idx) >> np.uint64(11)
+    return np.exp(2j * np.pi * (ph.astype(np.float64) * 2.0 ** -53))
+
+
+def channel(x, gain=1.0, nco=(0, 0), n0=0.0, seed=0, s0=0, rotate=rotate):
     """y for the (n, 2) samples x (any float dtype, widened exactly). gain and sqrt(n0) enter as
-    the f32 values the handle holds. Returns (y (n, 2) float64, r (n,): sqrt(-ln u1), or zeros)."""
+    the f32 values the handle holds. Returns (y (n, 2) float64, r (n,): sqrt(-ln u1), or zeros).
+    `rotate`: rotate, or rotate_np for long streams."""
     x = np.asarray(x)
     n = x.shape[0]
     xc = x[:, 0].astype(np.float64) + 1j * x[:, 1].astype(np.float64)

@@ -88,6 +88,70 @@ def sync(x, power, block, norm, ref, phase0, flat=False):
     return dict(out=derotate(x, ph), theta=theta, q=q, turn=turn, Phi=Phi, margins=margins, ph=ph)
 
 
+# ------------------------------------------------- the same steps for millions of symbols ----
+# numpy uint64 / int64 wrap-around arithmetic in place of the Python integers, a cumsum in place of
+# the recurrences. tests/test_sync_host.py holds every one equal to the function above it, element
+# for element; that equality is what lets tests/test_gpu_second_trip.py use them.
+def _u64(v):
+    return np.asarray(v, dtype=np.uint64)
+
+
+def estimates_np(x, power, block, norm, ref):
+    """estimates() with Phi as a uint64 array."""
+    r = cplx(x)
+    nb = len(r) // block
+    z = (float(np.float32(norm)) * r[: nb * block].reshape(nb, block)) ** power
+    P, S = z.sum(1), np.abs(z).sum(1)
+    ok = np.isfinite(P) & np.isfinite(S) & (S > 0)
+    q = np.where(ok, np.abs(P) / np.where(ok, S, 1.0), 0.0)
+    turn = np.where(np.isfinite(P) & (P != 0), np.angle(P) / (2 * np.pi), 0.0) % 1.0
+    t32 = (np.rint(turn * 2.0 ** 32).astype(np.int64) & 0xFFFFFFFF).astype(np.uint64)
+    return q, turn, (t32 << np.uint64(32)) - np.uint64(ref & MASK)
+
+
+def unwrap_np(Phi, power, phase0):
+    """unwrap() on a uint64 array: (theta uint64 (nb,), margins float64 (nb,))."""
+    Phi = _u64(Phi)
+    lm = power.bit_length() - 1
+    prev = np.concatenate([_u64([(power * phase0) & MASK]), Phi])[: len(Phi)]
+    d = (Phi - prev).view(np.int64)
+    theta = np.uint64(phase0 & MASK) + np.cumsum((d >> lm).view(np.uint64), dtype=np.uint64)
+    return theta, 0.5 - np.abs(d.astype(np.float64)) / 2.0 ** 64
+
+
+def phases_np(theta, block, phase0, flat=False, nflush=0):
+    """phases() on a uint64 array of theta: uint64 (nb * block + nflush,)."""
+    theta = _u64(theta)
+    lb = block.bit_length() - 1
+    d = np.zeros(len(theta), np.int64)
+    d[1:] = (theta[1:] - theta[:-1]).view(np.int64)
+    s = np.zeros_like(d) if flat else d >> (lb + 1)
+    i = 2 * np.arange(block, dtype=np.int64) - block + 1
+    ph = (theta[:, None] + (s[:, None] * i[None, :]).view(np.uint64)).reshape(-1)
+    th, sl = (theta[-1], s[-1]) if len(theta) else (np.uint64(phase0 & MASK), np.int64(0))
+    f = 2 * (np.arange(nflush, dtype=np.int64) + block) - block + 1
+    return np.concatenate([ph, th + (sl * f).view(np.uint64)])
+
+
+def derotate_np(x, ph):
+    """derotate() on a uint64 array of phases."""
+    a = (_u64(ph) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+    y = cplx(x) * np.exp(-2j * np.pi * a)
+    return np.stack([y.real, y.imag], 1)
+
+
+def top32_np(ph):
+    return _u64(ph) & np.uint64(0xFFFFFFFF00000000)
+
+
+def sync_np(x, power, block, norm, ref, phase0, flat=False):
+    """sync() from the variants above: arrays where sync() has lists."""
+    q, turn, Phi = estimates_np(x, power, block, norm, ref)
+    theta, margins = unwrap_np(Phi, power, phase0)
+    ph = phases_np(theta, block, phase0, flat, len(x) - len(theta) * block)
+    return dict(out=derotate_np(x, ph), theta=theta, q=q, turn=turn, Phi=Phi, margins=margins, ph=ph)
+
+
 # ------------------------------------------------- the loopback of the two test files ----
 # QPSK(0, 1) / QAM16 through a 65-tap RRC at sps 4, the channel's offset and phase, 2^17 bits: the
 # conditions of tests/test_gpu_sync_loopback.py, confirmed on the oracle's chain in

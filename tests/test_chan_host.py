@@ -242,3 +242,17 @@ def test_oracle_loopback_is_in_the_band(m, o):
     errors = int(np.sum((x_or >> 1) + (x_or & 1)))
     print(f"oracle loopback: {errors} bit errors, expected {want:.0f} +- {band:.0f} (5 sigma)")
     assert abs(errors - want) <= band
+
+
+def test_the_vectorised_rotation_equals_the_restatement():
+    """chan_ref.rotate_np (numpy uint64) against chan_ref.rotate (Python integers), bit for bit."""
+    rng = np.random.RandomState(5)
+    for _ in range(20):
+        step, phase0, s0 = (int(rng.randint(0, 1 << 32)) << 32 | int(rng.randint(0, 1 << 32)) for _ in range(3))
+        assert chan_ref.rotate(step, phase0, s0, 300).tobytes() == chan_ref.rotate_np(step, phase0, s0, 300).tobytes()
+    for s0 in (0, 1, (1 << 40) + 3, (1 << 64) - 2):
+        assert chan_ref.rotate(3, 5, s0, 64).tobytes() == chan_ref.rotate_np(3, 5, s0, 64).tobytes()
+    x = rng.randn(200, 2).astype(np.float32)
+    kw = dict(gain=0.37, nco=(0x123456789ABCDEF1, 0xFEDCBA9876543210), n0=0.35, seed=99, s0=(1 << 40) + 3)
+    a, b = chan_ref.channel(x, **kw), chan_ref.channel(x, rotate=chan_ref.rotate_np, **kw)
+    assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()

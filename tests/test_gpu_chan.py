@@ -59,9 +59,10 @@ def bound(x, r, gain, n0, ref, out_dtype):
     return b
 
 
-def run_parity(m, torch, x, kw, s0, in_dtype, out_dtype, tag, offset=0):
+def run_parity(m, torch, x, kw, s0, in_dtype, out_dtype, tag, offset=0, rotate=chan_ref.rotate):
     """x: float32 scatter; the kernel reads x[offset:] as in_dtype from a buffer whose start is
-    16-byte aligned (offset 1: 8-byte but not 16-byte aligned for f32)."""
+    16-byte aligned (offset 1: 8-byte but not 16-byte aligned for f32). `rotate`: chan_ref.rotate_np
+    for millions of samples (tests/test_chan_host.py holds it equal to chan_ref.rotate)."""
     xin = x.astype(NP_DT[in_dtype])
     dev = torch.from_numpy(xin).cuda()
     assert dev.data_ptr() % 16 == 0
@@ -69,13 +70,14 @@ def run_parity(m, torch, x, kw, s0, in_dtype, out_dtype, tag, offset=0):
     got = ch.process(dev[offset:]).cpu().numpy().astype(np.float64)
     assert ch.sample == s0 + len(x) - offset
     ref, r = chan_ref.channel(xin[offset:], gain=kw.get("gain", 1.0), nco=ch.nco, n0=kw.get("n0", 0.0),
-                              seed=kw.get("seed", 0), s0=s0)
+                              seed=kw.get("seed", 0), s0=s0, rotate=rotate)
     b = bound(xin[offset:], r, kw.get("gain", 1.0), kw.get("n0", 0.0), ref, out_dtype)
     ratio = float((np.abs(got - ref) / b).max())
     line = f"{tag:44s} n {len(x) - offset:5d}  worst ratio {ratio:.3f}"
     print(line)
     MARGINS.append(line)
     assert ratio <= 1.0, line
+    return got
 
 
 @pytest.mark.parametrize("n", SIZES)

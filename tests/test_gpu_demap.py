@@ -117,6 +117,34 @@ def _check_f32(got, ref, bound, what):
     assert np.all(err <= bound), f"{what}: {int(np.sum(err > bound))} of {err.size} outside the bound (worst {worst:.3f}x)"
 
 
+def _check_f16(g, ref, bound):
+    """f16 output (float64 copy g): finite, exactly +-65504 where |ref| > 70000, the f32 bound +
+    2^-11 |ref| + 2^-25 below 0.99 * 65504, and no reference value between the two rules."""
+    a = np.abs(ref)
+    sat, inside = a > 70000, a < 0.99 * 65504
+    assert np.all(sat | inside)
+    assert np.all(np.isfinite(g))
+    assert np.array_equal(g[sat], np.sign(ref[sat]) * 65504.0)
+    err = np.abs(g - ref)[inside]
+    lim = (bound + 2.0 ** -11 * a + 2.0 ** -25)[inside]
+    print(f"f16 out: max err / bound = {np.max(err / lim):.3f}")
+    assert np.all(err <= lim)
+    return sat, inside
+
+
+def _check_i8(g, ref, bound):
+    """int8 output (float64 copy g): within 1 of q = rint(clip(ref, -127, 127)) everywhere, equal to
+    it wherever ref lies further than the f32 bound from a half-integer (at most 1 % lie closer)."""
+    q = np.rint(np.clip(ref, -127, 127))
+    near = np.abs(ref - (np.floor(ref) + 0.5)) <= bound
+    print(f"i8 out: ref in [{ref.min():.4g}, {ref.max():.4g}], {near.mean() * 100:.3f} % near a half-integer")
+    assert ref.min() < -127.5 and ref.max() > 127.5 and np.any(np.abs(ref) < 100)
+    assert near.mean() <= 0.01
+    assert np.all(np.abs(g - q) <= 1)
+    assert np.array_equal(g[~near], q[~near])
+    assert g.min() == -127 and g.max() == 127
+
+
 # ----------------------------------------------------------------------------- parity ----
 @pytest.mark.parametrize("kind", [str(n) for n in NSYMS] + ["special"])
 @pytest.mark.parametrize("name", list(CONSTELLATIONS))
@@ -193,13 +221,7 @@ def test_f16_output_saturates(m, torch_cuda):
     dm = m.QAM(4, 0.0, 1.0).demapper(out_dtype=m.DTYPE_F16)
     got = dm.process(torch.tensor(iq, device="cuda"), F16_SCALE)
     assert got.dtype == torch.float16
-    g = got.cpu().numpy().astype(np.float64)
-    assert np.all(np.isfinite(g))
-    assert np.array_equal(g[sat], np.sign(ref[sat]) * 65504.0)
-    err = np.abs(g - ref)[inside]
-    lim = (bound + 2.0 ** -11 * a + 2.0 ** -25)[inside]
-    print(f"f16 out: max err / bound = {np.max(err / lim):.3f}")
-    assert np.all(err <= lim)
+    _check_f16(got.cpu().numpy().astype(np.float64), ref, bound)
 
 
 I8_SCALE = 256.0
@@ -217,18 +239,10 @@ def test_i8_output(m, torch_cuda, path):
     further than the f32 bound from a half-integer (at most 1 % of the elements lie closer)."""
     torch = torch_cuda
     iq, ref, bound = i8_case()
-    q = np.rint(np.clip(ref, -127, 127))
-    near = np.abs(ref - (np.floor(ref) + 0.5)) <= bound
-    print(f"i8 out: ref in [{ref.min():.4g}, {ref.max():.4g}], {near.mean() * 100:.3f} % near a half-integer")
-    assert ref.min() < -127.5 and ref.max() > 127.5 and np.any(np.abs(ref) < 100)
-    assert near.mean() <= 0.01
     dm = m.QAM(4, 0.0, 1.0).demapper(out_dtype=m.DTYPE_I8, path=m.DEMAP_GENERAL if path == "general" else m.DEMAP_AUTO)
     got = dm.process(torch.tensor(iq, device="cuda"), I8_SCALE)
     assert got.dtype == torch.int8 and tuple(got.shape) == ref.shape
-    g = got.cpu().numpy().astype(np.float64)
-    assert np.all(np.abs(g - q) <= 1)
-    assert np.array_equal(g[~near], q[~near])
-    assert g.min() == -127 and g.max() == 127
+    _check_i8(got.cpu().numpy().astype(np.float64), ref, bound)
 
 
 # ------------------------------------------------------------------ chunks and buffers ----

@@ -97,13 +97,17 @@ def out_bound(x, out_dtype):
     return np.repeat(b[:, None], 2, 1)
 
 
-def run_parity(m, torch, name, in_dtype, out_dtype, flat=False):
-    x32, power, block = stream(m, name)
+def run_parity(m, torch, name, in_dtype, out_dtype, flat=False, block=None, nsym=None, fast=False):
+    """`block`, `nsym`: another shape of the case's stream. `fast`: the vectorised restatement
+    (tests/test_sync_host.py holds it equal to the one used otherwise), for millions of symbols."""
+    sync_fn, phases_fn, derotate_fn, top32_fn = ((sync_ref.sync_np, sync_ref.phases_np, sync_ref.derotate_np, sync_ref.top32_np) if fast else
+                                                 (sync_ref.sync, sync_ref.phases, sync_ref.derotate, sync_ref.top32))
+    x32, power, block = stream(m, name, block, nsym)
     xin = x32.astype(NP_DT[in_dtype])
     sy = make_sync(m, name, block, in_dtype=in_dtype, out_dtype=out_dtype, flags=m.SYNC_FLAT if flat else 0)
     assert sy.power == power
     ref, phase0 = sync_ref.turns(m, sy.ref_phase), sync_ref.turns(m, PHASE0)
-    want = sync_ref.sync(xin, power, block, sy.norm, ref, phase0, flat)
+    want = sync_fn(xin, power, block, sy.norm, ref, phase0, flat)
     nb = len(xin) // block
     assert want["q"].min() >= 0.3 and min(want["margins"]) >= 0.1          # the inputs keep clear of every branch cut
     out, theta, q = sy.process(torch.from_numpy(xin).cuda())
@@ -121,8 +125,8 @@ def run_parity(m, torch, name, in_dtype, out_dtype, flat=False):
     assert sync_ref.unwrap(phi, power, phase0)[0] == th
     # out: the float64 rotation by the device's own integers
     got = np.concatenate([out.cpu().numpy(), rest.cpu().numpy()]).astype(np.float64)
-    ph = sync_ref.phases(th, block, phase0, flat, len(xin) - nb * block)
-    rot = sync_ref.derotate(xin, sync_ref.top32(ph))
+    ph = phases_fn(th, block, phase0, flat, len(xin) - nb * block)
+    rot = derotate_fn(xin, top32_fn(ph))
     r_out = float((np.abs(got - rot) / out_bound(xin, out_dtype)).max())
     assert np.all(np.isfinite(got))
     names = {0: "f32", 1: "f16"}

@@ -64,11 +64,14 @@ def out_bound(taps, want, out_dtype):
     return b
 
 
-def check(m, torch, x, sps, block, span, tau0, in_dtype, out_dtype, flat=False, label=""):
-    """One stream through process and flush, held against the restatement. Returns (want, D, got)."""
+def check(m, torch, x, sps, block, span, tau0, in_dtype, out_dtype, flat=False, label="", fast=False):
+    """One stream through process and flush, held against the restatement. Returns (want, D, got).
+    `fast`: the vectorised restatement (tests/test_timing_host.py holds it equal to the one used
+    otherwise), for millions of samples."""
+    timing_fn, positions_fn = (R.timing_np, R.positions_np) if fast else (R.timing, R.positions)
     xin = np.asarray(x).astype(NP_DT[in_dtype])
     z = R.cplx(xin)
-    want = R.timing(z, sps, block, span, tau0, flat)
+    want = timing_fn(z, sps, block, span, tau0, flat)
     ts = m.TimingSync(sps, block=block, span=span, tau0=tau0, flat=flat, in_dtype=in_dtype, out_dtype=out_dtype)
     out, tau, q = ts.process(torch.from_numpy(xin).cuda())
     rest = ts.flush(like=out)
@@ -80,7 +83,7 @@ def check(m, torch, x, sps, block, span, tau0, in_dtype, out_dtype, flat=False, 
     phi = [d & 0xFFFFFFFF for d in D]
     assert R.unwrap(phi, R.d_start(tau0))[0] == D                      # tau: the recurrence on the device's own Phi
     qd = q.cpu().numpy().astype(np.float64)
-    mpos, mu24 = R.positions(D, R.d_start(tau0), sps, block, span, flat, nfl)
+    mpos, mu24 = positions_fn(D, R.d_start(tau0), sps, block, span, flat, nfl)
     ref, taps = R.interpolate(z, mpos, mu24)
     got = np.concatenate([out.cpu().numpy(), rest.cpu().numpy()]).astype(np.float64)
     assert np.all(np.isfinite(got))
@@ -88,9 +91,10 @@ def check(m, torch, x, sps, block, span, tau0, in_dtype, out_dtype, flat=False, 
     return want, D, got, qd, r_out
 
 
-def run_parity(m, torch, name, in_dtype, out_dtype, flat=False):
-    x, sps, block = R.case_stream(name)
-    want, D, got, qd, r_out = check(m, torch, x, sps, block, R.CASE_SPAN, R.CASE_TAU0, in_dtype, out_dtype, flat)
+def run_parity(m, torch, name, in_dtype, out_dtype, flat=False, case=None, fast=False):
+    """`case`: (x, sps, block) of another stream in place of R.case_stream(name); `fast` as in check()."""
+    x, sps, block = case or R.case_stream(name)
+    want, D, got, qd, r_out = check(m, torch, x, sps, block, R.CASE_SPAN, R.CASE_TAU0, in_dtype, out_dtype, flat, fast=fast)
     assert want["q"].min() >= 0.02 and min(want["margins"]) >= 0.1         # the inputs keep clear of every branch cut
     d = np.array([(v & 0xFFFFFFFF) / 2.0 ** 32 for v in D]) - want["turn"]
     d = np.abs(d - np.round(d))

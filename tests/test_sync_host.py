@@ -215,3 +215,36 @@ def test_reference_meets_the_qam16_loopback_conditions(m, o):
           f"{_bit_errors(r['out'], lut, sent)} bit errors")
     assert len(r["theta"]) == 128
     assert worst < 1 / 16
+
+
+# ------------------------------------------------------- the vectorised restatement ----
+@pytest.mark.parametrize("in_dtype", [0, 1])
+@pytest.mark.parametrize("flat", [False, True])
+@pytest.mark.parametrize("name", ["bpsk", "qpsk", "qam16", "8psk"])
+def test_the_vectorised_restatement_equals_the_restatement(m, name, flat, in_dtype):
+    """sync_ref's *_np variants against the functions they restate, element for element, on the
+    streams of tests/test_gpu_sync.py (the flush included), on a stream with a wrap in every
+    block, and on the degenerate shapes."""
+    import test_gpu_sync as G
+    x32, power, block = G.stream(m, name)
+    x = x32.astype(G.NP_DT[in_dtype])
+    sy = dict(bpsk=m.BPSK(0.7853982, 1.0), qpsk=m.QPSK(0.0, 1.0), qam16=m.QAM(4, 0.0, 1.0), **{"8psk": m.MPSK(3, 0.0, 1.0)})[name]
+    _, norm, ref_phase = m._sync_params(sy.lut())
+    ref, phase0 = sync_ref.turns(m, ref_phase), sync_ref.turns(m, G.PHASE0)
+    for xs in (x, x[: block - 1], x[:block], x[:0]):
+        a = sync_ref.sync(xs, power, block, norm, ref, phase0, flat)
+        b = sync_ref.sync_np(xs, power, block, norm, ref, phase0, flat)
+        assert b["Phi"].dtype == np.uint64 and b["theta"].dtype == np.uint64 and b["ph"].dtype == np.uint64
+        for key in ("Phi", "theta", "ph"):
+            assert [int(v) for v in b[key]] == a[key], key
+        assert np.array_equal(np.asarray(a["margins"], np.float64), b["margins"])
+        for key in ("q", "turn", "out"):
+            assert a[key].tobytes() == b[key].tobytes(), key
+        assert [int(v) for v in sync_ref.top32_np(b["ph"])] == sync_ref.top32(a["ph"])
+    # arbitrary 64-bit Phi: every wrap, both signs, the shifts of negative differences
+    rng = np.random.RandomState(power + flat)
+    Phi = [int(v) for v in rng.randint(0, 1 << 32, 300).astype(np.uint64) << np.uint64(32) | rng.randint(0, 1 << 32, 300).astype(np.uint64)]
+    th, mg = sync_ref.unwrap(Phi, power, phase0)
+    th_np, mg_np = sync_ref.unwrap_np(np.array(Phi, np.uint64), power, phase0)
+    assert [int(v) for v in th_np] == th and np.array_equal(np.asarray(mg), mg_np)
+    assert [int(v) for v in sync_ref.phases_np(th_np, block, phase0, flat, 5)] == sync_ref.phases(th, block, phase0, flat, 5)

@@ -260,3 +260,36 @@ def test_reference_qam16_loopback_delay(m, o):
     print(line)
     FIGURES.append(line)
     assert len(tau) == 32 and worst <= C["tau_margin"]
+
+
+# ------------------------------------------------------- the vectorised restatement ----
+@pytest.mark.parametrize("in_dtype", [0, 1])
+@pytest.mark.parametrize("flat", [False, True])
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_the_vectorised_restatement_equals_the_restatement(name, flat, in_dtype):
+    """timing_ref's *_np variants against the functions they restate, element for element, on the
+    streams of tests/test_gpu_timing.py (the flush included), on the degenerate shapes, on random
+    32-bit Phi (every wrap) and on delays beyond the span (the clamp)."""
+    x32, sps, block = R.case_stream(name)
+    z = R.cplx(x32.astype(np.float16 if in_dtype else np.float32))
+    bn = block * sps
+    for zs in (z, z[: bn - 1], z[:bn], z[: bn + sps + 1], z[:0]):
+        a = R.timing(zs, sps, block, R.CASE_SPAN, R.CASE_TAU0, flat)
+        b = R.timing_np(zs, sps, block, R.CASE_SPAN, R.CASE_TAU0, flat)
+        for key in ("Phi", "D"):
+            assert b[key].dtype == np.int64 and [int(v) for v in b[key]] == a[key], key
+        assert np.array_equal(np.asarray(a["margins"], np.float64), b["margins"])
+        for key in ("q", "turn", "out", "taps", "m", "mu24"):
+            assert a[key].shape == b[key].shape and a[key].tobytes() == b[key].tobytes(), key
+    rng = np.random.RandomState(block + sps + flat)
+    Phi = [int(v) for v in rng.randint(0, 1 << 32, 300)]
+    for start in (R.d_start(R.CASE_TAU0), -(5 << 32) - 12345, (7 << 32) + 99):
+        D, mg = R.unwrap(Phi, start)
+        D_np, mg_np = R.unwrap_np(Phi, start)
+        assert [int(v) for v in D_np] == D and np.array_equal(np.asarray(mg), mg_np)
+        for first in (True, False):
+            pa = R.positions(D, start, sps, block, 1, flat, 7, first)
+            pb = R.positions_np(D_np, start, sps, block, 1, flat, 7, first)
+            assert np.array_equal(pa[0], pb[0]) and np.array_equal(pa[1], pb[1])
+    pa, pb = R.positions([], 12345, sps, block, 2, flat, 9), R.positions_np([], 12345, sps, block, 2, flat, 9)
+    assert np.array_equal(pa[0], pb[0]) and np.array_equal(pa[1], pb[1])

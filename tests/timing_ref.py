@@ -143,6 +143,68 @@ def timing(x, sps, block, span, tau0, flat=False):
     return dict(out=out, taps=taps, D=D, q=q, turn=turn, Phi=Phi, margins=margins, m=m, mu24=mu24)
 
 
+# ------------------------------------------------- the same steps for millions of samples ----
+# int64 arrays and a cumsum in place of the per-block Python loops. tests/test_timing_host.py holds
+# every one equal to the function above it, element for element; that equality is what lets
+# tests/test_gpu_second_trip.py use them.
+def estimates_np(x, sps, block):
+    """estimates() with Phi as an int64 array."""
+    nb = len(x) // (block * sps)
+    e = (np.abs(x[: nb * block * sps]) ** 2).reshape(nb, block, sps).sum(1)
+    S = e.sum(1)
+    X = (e * np.exp(-2j * np.pi * np.arange(sps) / sps)).sum(1)
+    ok = np.isfinite(X) & np.isfinite(S) & (S > 0)
+    q = np.where(ok, np.abs(X) / np.where(ok, S, 1.0), 0.0)
+    turn = np.where(np.isfinite(X) & (X != 0), -np.angle(X) / (2 * np.pi), 0.0) % 1.0
+    return q, turn, np.rint(turn * 2.0 ** 32).astype(np.int64) & 0xFFFFFFFF
+
+
+def unwrap_np(Phi, D_start):
+    """unwrap() on an array: (D int64 (nb,), margins float64 (nb,)). D_b - D_start is the running
+    sum of the wraps w_b, and w_b = sext32(Phi_b - D_{b-1}) depends only on the low 32 bits of
+    D_{b-1}, which are Phi_{b-1}: w_b = sext32(Phi_b - Phi_{b-1})."""
+    Phi = np.asarray(Phi, dtype=np.int64)
+    prev = np.concatenate([np.array([int(D_start)], np.int64), Phi])[: len(Phi)]
+    w = ((Phi - prev) & 0xFFFFFFFF)
+    w = w - ((w >> 31) << 32)
+    return int(D_start) + np.cumsum(w), 0.5 - np.abs(w) / 2.0 ** 32
+
+
+def positions_np(D, D_start, sps, block, span, flat=False, nflush=0, first=True):
+    """positions() on an int64 array of D."""
+    D = np.asarray(D, dtype=np.int64)
+    lb = block.bit_length() - 1
+    lim = span * ONE
+    prev = np.concatenate([np.array([int(D_start)], np.int64), D])[: len(D)]
+    d = D - prev
+    if first and len(d):
+        d[0] = 0
+    s = np.zeros_like(d) if flat else d >> (lb + 1)
+    i = np.arange(block, dtype=np.int64)
+    e = np.clip(D[:, None] + s[:, None] * (2 * i - block + 1)[None, :], -lim, lim)
+    Q = sps * ((i[None, :] - span) * ONE + e)
+    ms = (np.arange(len(D), dtype=np.int64) * (block * sps))[:, None] + (Q >> 32)
+    ms, mus = ms.reshape(-1), ((Q & 0xFFFFFFFF) >> 8).reshape(-1)
+    if nflush:
+        cur, sl = (int(D[-1]), int(s[-1])) if len(D) else (int(D_start), 0)
+        f = np.arange(nflush, dtype=np.int64)
+        e = np.clip(cur + sl * (2 * (f + block) - block + 1), -lim, lim)
+        Q = sps * ((f - span) * ONE + e)
+        ms = np.concatenate([ms, len(D) * block * sps + (Q >> 32)])
+        mus = np.concatenate([mus, (Q & 0xFFFFFFFF) >> 8])
+    return ms, mus
+
+
+def timing_np(x, sps, block, span, tau0, flat=False):
+    """timing() from the variants above: arrays where timing() has lists."""
+    q, turn, Phi = estimates_np(x, sps, block)
+    D, margins = unwrap_np(Phi, d_start(tau0))
+    nflush = (len(x) - len(D) * block * sps) // sps
+    m, mu24 = positions_np(D, d_start(tau0), sps, block, span, flat, nflush)
+    out, taps = interpolate(x, m, mu24)
+    return dict(out=out, taps=taps, D=D, q=q, turn=turn, Phi=Phi, margins=margins, m=m, mu24=mu24)
+
+
 # ------------------------------------------------------------------ the bounds ----
 U = 2.0 ** -24
 
