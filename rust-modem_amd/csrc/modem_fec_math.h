@@ -3,7 +3,7 @@
 // encoder step, the quantiser of the decoder's input, the predecessor of a trellis state and the
 // branch word of a state (the coded bits of its two incoming branches). Compiles for the device and
 // for a plain host compiler, as modem_scan_step.h does: the kernels of modem_fec.hip, the handle's
-// table in modem_capi.cpp and the host decoder of tests/cpp/fec_host.cpp all read this text. All of
+// table in capi_fec.cpp and the host decoder of tests/cpp/fec_host.cpp all read this text. All of
 // it is integer arithmetic but the one f32 product of the quantiser.
 #pragma once
 

@@ -1,5 +1,5 @@
 // rust-modem_amd/csrc/modem_internal.h — kernel parameter blocks and launchers shared by
-// modem_kernels.hip (device code) and modem_capi.cpp (the C ABI). Not part of the ABI.
+// modem_kernels.hip (device code) and capi_*.cpp (the C ABI). Not part of the ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,7 +10,7 @@ namespace mk {
 
 // The RX MFMA kernels walk a call's tiles in rounds from the top down (rx_mfma_body), so the
 // last samples a TX launch wrote are the first the RX reads. The TX store policy relies on it
-// (modem_capi.cpp tx_nt_below: a single-channel launch of <= 256 MiB keeps its second half
+// (capi_tx.cpp tx_nt_below: a single-channel launch of <= 256 MiB keeps its second half
 // cacheable); rx_mfma_body asserts it. Changing the RX walk means revisiting that policy.
 constexpr bool kRxTilesTopDown = true;
 

@@ -1,6 +1,6 @@
 """BASELINE config 5's own launch shape (VERDICT r03 Missing 3): ONE period of 256-QAM, 513-tap RRC
 at sps 8 over 2^26 complex f32 samples through the bench's step (ChainPlan: modem_chain_run), so
-the TX is a single 512 MiB launch with non-temporal stores (modem_capi.cpp tx_nt_below) and the
+the TX is a single 512 MiB launch with non-temporal stores (capi_tx.cpp tx_nt_below) and the
 RX a single launch over it with 2^23 - 64 kept instants in one grid walk.
 
   * every decision equals the symbol sent (the loopback property of SURVEY.md §8c; reference

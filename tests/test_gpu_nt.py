@@ -1,4 +1,4 @@
-"""Non-temporal TX stores (rust-modem_amd/csrc/modem_capi.cpp tx_nt_below): a TX launch whose
+"""Non-temporal TX stores (rust-modem_amd/csrc/capi_tx.cpp tx_nt_below): a TX launch whose
 output exceeds 192 MiB stores its samples non-temporally (a single-channel launch of at most
 256 MiB, as here, its first half: both store paths in one call). The store policy must not
 change a single sample:
