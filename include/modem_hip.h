@@ -797,7 +797,7 @@ modem_status modem_frame_gather(const void* iq, size_t nsym, uint64_t base, cons
  *      F32, F16:  q = (int) rintf(fminf(fmaxf(v * qscale, -127.f), 127.f))
  *    F16 widened exactly, the product one f32 multiply, ties to even; qscale finite and positive.
  *    A NaN is unspecified (and memory-safe). q = 0 is an erasure: a caller depunctures by inserting
- *    zeros.
+ *    zeros (modem_rm_rx below does).
  * 3. Path metrics are int32 correlations, maximised: pm[0] = 0 at the start of a frame, every
  *    other state -2^30. State s' at step t+1 has the input bit b = s' >> (K-2) and the two
  *    predecessors p_x = ((s' << 1) & (S-1)) | x, x in {0, 1};
@@ -840,6 +840,70 @@ modem_status modem_viterbi_create(uint32_t K, const uint32_t* polys, uint32_t n,
 modem_status modem_viterbi_process(modem_viterbi* h, const void* llr, size_t stride, size_t nframes, size_t nbits, float qscale,
                                    const uint8_t* ok, uint8_t* out, size_t out_stride, int32_t* metric, void* stream);
 modem_status modem_viterbi_destroy(modem_viterbi* h);
+
+/* ---- Rate matching and frame check (GLUE: the reference has none) ---------------------------- */
+/* What a coded frame needs around the convolutional code: puncturing to a higher rate, a block
+ * interleaver that spreads the bursts the receive chain makes, and a CRC that says whether a frame
+ * decoded right. The chain is
+ *   bits -> crc attach -> conv encode -> rm tx -> tx ... rx -> ... -> gather -> demapper
+ *        -> rm rx -> viterbi(ok) -> crc check(ok) -> ok'
+ * Everything is an integer rule on independent frames, so every output value is specified exactly.
+ * The entries are stateless: the pattern and the CRC's parameters are passed by value with each
+ * call (pattern is host memory, read before the call returns); nothing is kept on the device.
+ *
+ * 1. Puncturing. pattern[0..P-1], bytes that are 0 or 1, 1 <= P <= 64, weight w = sum pattern >= 1.
+ *    A frame has Nm mother indices, 1 <= Nm <= 16384 (the n * T of modem_conv_encode's row). Index
+ *    m, 0 <= m < Nm, is kept iff pattern[m mod P] == 1, and a kept m has the rank
+ *      j = (m / P) * w + #{i < m mod P : pattern[i] == 1}.
+ *    E = #{kept m < Nm}; a pattern with E == 0 for the Nm of the call is INVALID_ARG. For the K = 7
+ *    pair (0171, 0133), coded bit t*n + j: rate 2/3 is (1,1,1,0), rate 3/4 is (1,1,1,0,0,1).
+ * 2. Interleaving, over the E kept values: cols = C, 1 <= C <= 256; rows = ceil(E / C);
+ *    cl = E - (rows - 1) * C (1 .. C, the cells of the last row). Input j sits at r = j / C,
+ *    c = j mod C; the block is written by rows and read by columns, the absent cells of the last
+ *    row skipped:
+ *      pi(j) = c * rows + r - max(0, c - cl),
+ *    a bijection on 0 .. E-1; C = 1 is the identity. Mother index m is transmitted at position
+ *    pi(rank(m)).
+ * 3. modem_rm_tx: bits is nframes rows of Nm bytes, row stride in_stride >= Nm; out is rows of E
+ *    bytes, row stride out_stride >= E: out[f][pi(rank(m))] = bits[f][m] & 1 for every kept m.
+ *    Nothing is written past E in a row.
+ * 4. modem_rm_rx: llr is rows of E values of dtype (F32, F16 or I8), out rows of Nm values of the
+ *    same dtype, strides in elements: out[f][m] = llr[f][pi(rank(m))] for a kept m, moved as bits
+ *    with no arithmetic (a NaN payload, a -0 and a -128 arrive unchanged); a punctured m gets the
+ *    dtype's +0 (all bits zero), the decoder's erasure. Nothing is written past Nm in a row. ok may
+ *    be NULL; otherwise nframes bytes of device memory, accepted so that the chain's calls look
+ *    alike, and ignored: every row is moved (the decoder behind it skips the rows with ok == 0).
+ * 5. The CRC: width W in {8, 16, 24, 32}; poly (the top bit x^W implicit), init and xorout below
+ *    2^W. No reflection: the message is the row's bytes in order, first byte first, bit 0 of each
+ *    byte. One step per message bit b:
+ *      fb = (reg >> (W-1)) ^ b;   reg = (reg << 1) mod 2^W;   if fb: reg ^= poly
+ *    reg starts at init; the CRC is reg ^ xorout. The 72 bits of "123456789", MSB of each character
+ *    first, give 0x29B1 for (16, 0x1021, 0xFFFF, 0) and 0x0376E6E7 for (32, 0x04C11DB7, 0xFFFFFFFF, 0).
+ * 6. modem_crc_attach: bits is rows of nbits bytes, 1 <= nbits <= 65536; out rows of nbits + W
+ *    bytes: out[f][i] = bits[f][i] & 1 for i < nbits, then the CRC of those nbits, most significant
+ *    bit first. Nothing is written past nbits + W in a row.
+ * 7. modem_crc_check: bits is rows of nbits + W bytes (the decoder's output); ok_in is NULL or
+ *    nframes bytes; ok_out[f] = 1 iff (ok_in == NULL or ok_in[f] != 0) and the CRC of the first
+ *    nbits equals the W bits that follow (bit 0 of each byte), else 0. ok_out == ok_in is allowed.
+ *    Nothing is read back.
+ *
+ * Arguments, all five entries: bad P, pattern byte, weight, cols, Nm, E == 0, W, poly, init,
+ * xorout, nbits, dtype, a row stride smaller than its row, a NULL pattern or (with nframes > 0) a
+ * NULL buffer (ok and ok_in excepted), or input and output byte ranges that overlap (ok_out ==
+ * ok_in excepted): INVALID_ARG, before any device is looked at. Then a bad ordinal is NO_DEVICE.
+ * nframes == 0 succeeds and writes nothing. Every buffer is device memory of `device`, F16 and F32
+ * buffers aligned to their element; anything else is INVALID_ARG. The calls are asynchronous on
+ * `stream`. */
+/* *kept = E for the pattern and Nm (host only, no device). */
+modem_status modem_rm_kept(const uint8_t* pattern, uint32_t P, size_t nm, size_t* kept);
+modem_status modem_rm_tx(const uint8_t* pattern, uint32_t P, uint32_t cols, const uint8_t* bits, size_t nframes, size_t nm,
+                         size_t in_stride, uint8_t* out, size_t out_stride, int device, void* stream);
+modem_status modem_rm_rx(const uint8_t* pattern, uint32_t P, uint32_t cols, int32_t dtype, const void* llr, size_t nframes,
+                         size_t nm, size_t in_stride, const uint8_t* ok, void* out, size_t out_stride, int device, void* stream);
+modem_status modem_crc_attach(uint32_t W, uint32_t poly, uint32_t init, uint32_t xorout, const uint8_t* bits, size_t nframes,
+                              size_t nbits, size_t in_stride, uint8_t* out, size_t out_stride, int device, void* stream);
+modem_status modem_crc_check(uint32_t W, uint32_t poly, uint32_t init, uint32_t xorout, const uint8_t* bits, size_t nframes,
+                             size_t nbits, size_t in_stride, const uint8_t* ok_in, uint8_t* ok_out, int device, void* stream);
 
 /* ---- synthetic input (GLUE): splitmix64 bit stream, one byte per bit ------------------- */
 /* bit i = (word[i/64] >> (i%64)) & 1, word j = splitmix64 output j+1 from `seed`.

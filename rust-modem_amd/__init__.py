@@ -43,6 +43,7 @@ __all__ = [
     "TimingSync",
     "FrameSync",
     "ConvCode", "ViterbiDecoder", "CONV_TAIL",
+    "RateMatch", "CRC", "PUNCTURE_2_3", "PUNCTURE_3_4",
 ]
 
 PI32 = float(np.float32(math.pi))      # std::f32::consts::PI
@@ -216,6 +217,11 @@ def load_library():
         "modem_viterbi_create": (st, [u32, c.POINTER(u32), u32, u32, c.c_int32, c.c_int, c.POINTER(vp)]),
         "modem_viterbi_process": (st, [vp, vp, sz, sz, sz, f32, vp, vp, sz, vp, vp]),
         "modem_viterbi_destroy": (st, [vp]),
+        "modem_rm_kept": (st, [vp, u32, sz, c.POINTER(sz)]),
+        "modem_rm_tx": (st, [vp, u32, u32, vp, sz, sz, sz, vp, sz, c.c_int, vp]),
+        "modem_rm_rx": (st, [vp, u32, u32, c.c_int32, vp, sz, sz, sz, vp, vp, sz, c.c_int, vp]),
+        "modem_crc_attach": (st, [u32, u32, u32, u32, vp, sz, sz, sz, vp, sz, c.c_int, vp]),
+        "modem_crc_check": (st, [u32, u32, u32, u32, vp, sz, sz, sz, vp, vp, c.c_int, vp]),
         "modem_chain_create": (st, [vp, vp, vp, sz, vp, sz, vp, vp, sz, c.POINTER(vp)]),
         "modem_chain_run": (st, [vp, c.POINTER(sz), c.POINTER(sz), vp]),
         "modem_chain_fused": (c.c_int, [vp]),
@@ -1747,6 +1753,10 @@ class ConvCode:
     def decoder(self, in_dtype: int = DTYPE_I8, device: int = 0) -> "ViterbiDecoder":
         return ViterbiDecoder(self, in_dtype=in_dtype, device=device)
 
+    def rate_match(self, pattern: Sequence[int] = (1,), cols: int = 1, device: int = 0) -> "RateMatch":
+        """The `RateMatch` of a puncturing pattern over the code's bits (index t*n + j) and an interleaver."""
+        return RateMatch(pattern, cols=cols, device=device)
+
 
 class ViterbiDecoder:
     """Batched soft-decision Viterbi decoder of a `ConvCode` on the demapper's LLRs (positive =
@@ -1806,6 +1816,147 @@ class ViterbiDecoder:
         if getattr(self, "_h", None) and _lib is not None:
             _lib.modem_viterbi_destroy(self._h)
             self._h = None
+
+
+# ------------------------------------------------------ rate matching and frame check ----
+PUNCTURE_2_3 = (1, 1, 1, 0)                 # K = 7 (0171, 0133), coded bit t*n + j: rate 2/3
+PUNCTURE_3_4 = (1, 1, 1, 0, 0, 1)           # rate 3/4
+
+
+def _rows(x, names, what: str):
+    """(nframes, ncols, row stride in elements) of a 2-D CUDA tensor whose rows are contiguous: the
+    rows may be a view into a wider buffer (x = buf[:, :ncols]), and the stride is the tensor's."""
+    if not _is_torch(x) or not x.is_cuda or x.dim() != 2 or _dtype_name(x) not in names:
+        raise ValueError(f"{what} must be a 2-D CUDA tensor of {' / '.join(names)}")
+    nframes, ncols = int(x.shape[0]), int(x.shape[1])
+    if ncols and int(x.stride(1)) != 1:
+        raise ValueError(f"{what}: the elements of a row must be contiguous")
+    stride = int(x.stride(0)) if nframes > 1 else ncols
+    if stride < ncols:
+        raise ValueError(f"{what}: rows overlap (stride {stride} < {ncols})")
+    return nframes, ncols, stride
+
+
+class RateMatch:
+    """Puncturing and a pruned block interleaver between `ConvCode.encode` and the modulator, and
+    their inverse between the demapper and the `ViterbiDecoder` (GLUE: the reference has none;
+    include/modem_hip.h, "Rate matching and frame check").
+
+    `pattern`: 1 .. 64 values 0 / 1, at least one 1; mother index m of a frame is kept iff
+    pattern[m mod P] == 1 (`PUNCTURE_2_3`, `PUNCTURE_3_4` for the K = 7 pair). `cols`: 1 .. 256
+    columns of the interleaver over the kept values of a frame; 1 is none. `kept(nm)` is E, the
+    values of a frame of nm mother indices that are transmitted.
+    `tx(coded)`: (nframes, nm) uint8 -> (nframes, E) uint8, as `DigitalModulator.process` takes them
+    once flattened. `rx(llr, nm)`: (nframes, E) int8 / float16 / float32 -> (nframes, nm) of the same
+    dtype, every value moved as it is, a punctured position +0 (the decoder's erasure). Rows may be
+    views into wider buffers (the row stride is the tensor's); `out` likewise, and nothing is
+    written outside its rows. Asynchronous on `stream` (default: the current one)."""
+
+    PUNCTURE_2_3, PUNCTURE_3_4 = PUNCTURE_2_3, PUNCTURE_3_4
+
+    def __init__(self, pattern: Sequence[int] = (1,), cols: int = 1, device: int = 0):
+        self.pattern, self.cols, self.device = tuple(int(v) for v in pattern), int(cols), int(device)
+        if not 1 <= len(self.pattern) <= 64 or any(v not in (0, 1) for v in self.pattern) or not any(self.pattern):
+            raise ModemPanic(ERR_INVALID_ARG, f"RateMatch: pattern = {pattern}")
+        if not 1 <= self.cols <= 256:
+            raise ModemPanic(ERR_INVALID_ARG, f"RateMatch: cols = {cols}")
+        self._pat = (ctypes.c_uint8 * len(self.pattern))(*self.pattern)
+
+    def kept(self, nm: int) -> int:
+        e = ctypes.c_size_t(0)
+        _check(load_library().modem_rm_kept(self._pat, len(self.pattern), int(nm), ctypes.byref(e)), "RateMatch.kept")
+        return int(e.value)
+
+    def _out(self, out, ref, nframes, ncols, dtype, what):
+        if out is None:
+            import torch
+            return torch.empty((nframes, ncols), dtype=dtype, device=ref.device), ncols
+        n, c, stride = _rows(out, (_dtype_name(ref),), f"{what}: out")
+        if n != nframes or c < ncols or out.device != ref.device:
+            raise ValueError(f"{what}: out must be ({nframes}, >= {ncols}) on the input's device")
+        return out, stride
+
+    def tx(self, coded, out=None, stream=None):
+        nframes, nm, stride = _rows(coded, ("uint8",), "RateMatch.tx: coded")
+        e = self.kept(nm)
+        out, ostride = self._out(out, coded, nframes, e, coded.dtype, "RateMatch.tx")
+        device = _device_of(coded, self.device)
+        _check(load_library().modem_rm_tx(self._pat, len(self.pattern), self.cols, int(coded.data_ptr()) if nframes else None,
+                                          nframes, nm, stride, int(out.data_ptr()) if nframes else None, ostride, device,
+                                          _stream_handle(stream, device)), "RateMatch.tx")
+        return out
+
+    def rx(self, llr, nm: int, out=None, stream=None, ok=None):
+        nframes, e, stride = _rows(llr, ("int8", "float16", "float32"), "RateMatch.rx: llr")
+        nm = int(nm)
+        if e != self.kept(nm):
+            raise ValueError(f"RateMatch.rx: rows of {e} values, but {self.kept(nm)} of {nm} are kept")
+        if ok is not None and (not _is_torch(ok) or _dtype_name(ok) != "uint8" or int(ok.numel()) != nframes):
+            raise ValueError(f"RateMatch.rx: ok must be {nframes} uint8 flags on the device")
+        dtype = {"int8": DTYPE_I8, "float16": DTYPE_F16, "float32": DTYPE_F32}[_dtype_name(llr)]
+        out, ostride = self._out(out, llr, nframes, nm, llr.dtype, "RateMatch.rx")
+        device = _device_of(llr, self.device)
+        _check(load_library().modem_rm_rx(self._pat, len(self.pattern), self.cols, dtype, int(llr.data_ptr()) if nframes else None,
+                                          nframes, nm, stride, _ptr(ok), int(out.data_ptr()) if nframes else None, ostride,
+                                          device, _stream_handle(stream, device)), "RateMatch.rx")
+        return out
+
+
+class CRC:
+    """A CRC over the bits of a frame, one byte per bit (GLUE; include/modem_hip.h, "Rate matching and
+    frame check"): width 8, 16, 24 or 32, `poly` with the top bit implicit, `init`, `xorout`, no
+    reflection, the first bit of a row first. `attach(bits)`: (nframes, nbits) uint8 -> (nframes,
+    nbits + width): the bits, then the CRC, most significant bit first. `check(bits, ok=None)`:
+    (nframes, nbits + width) uint8 -> ok' (nframes,) uint8: 1 iff the trailing width bits are the
+    CRC of the bits before them and `ok` (the flags the decoder got; None: all ones) is not 0;
+    `out` may be `ok` itself. Only bit 0 of a byte counts. Asynchronous on `stream`; nothing is
+    read back."""
+
+    def __init__(self, width: int, poly: int, init: int = 0, xorout: int = 0):
+        self.width, self.poly, self.init, self.xorout = int(width), int(poly), int(init), int(xorout)
+        if self.width not in (8, 16, 24, 32) or any(not 0 <= v < 1 << self.width for v in (self.poly, self.init, self.xorout)):
+            raise ModemPanic(ERR_INVALID_ARG, f"CRC: width = {width}, poly = {poly:#x}, init = {init:#x}, xorout = {xorout:#x}")
+
+    @classmethod
+    def ccitt16(cls) -> "CRC":
+        return cls(16, 0x1021, 0xFFFF)
+
+    @classmethod
+    def mpeg32(cls) -> "CRC":
+        return cls(32, 0x04C11DB7, 0xFFFFFFFF)
+
+    def attach(self, bits, out=None, stream=None):
+        nframes, nbits, stride = _rows(bits, ("uint8",), "CRC.attach: bits")
+        if out is None:
+            import torch
+            out, ostride = torch.empty((nframes, nbits + self.width), dtype=torch.uint8, device=bits.device), nbits + self.width
+        else:
+            n, c, ostride = _rows(out, ("uint8",), "CRC.attach: out")
+            if n != nframes or c < nbits + self.width or out.device != bits.device:
+                raise ValueError(f"CRC.attach: out must be uint8 ({nframes}, >= {nbits + self.width}) on the input's device")
+        device = _device_of(bits, 0)
+        _check(load_library().modem_crc_attach(self.width, self.poly, self.init, self.xorout,
+                                               int(bits.data_ptr()) if nframes else None, nframes, nbits, stride,
+                                               int(out.data_ptr()) if nframes else None, ostride, device,
+                                               _stream_handle(stream, device)), "CRC.attach")
+        return out
+
+    def check(self, bits, ok=None, out=None, stream=None):
+        nframes, ncols, stride = _rows(bits, ("uint8",), "CRC.check: bits")
+        if ncols <= self.width:
+            raise ModemPanic(ERR_INVALID_ARG, f"CRC.check: rows of {ncols} bytes hold no message in front of {self.width} CRC bits")
+        for name, t in (("ok", ok), ("out", out)):
+            if t is not None and (not _is_torch(t) or not t.is_cuda or _dtype_name(t) != "uint8" or int(t.numel()) != nframes):
+                raise ValueError(f"CRC.check: {name} must be {nframes} uint8 flags on the device")
+        if out is None:
+            import torch
+            out = torch.empty((nframes,), dtype=torch.uint8, device=bits.device)
+        device = _device_of(bits, 0)
+        _check(load_library().modem_crc_check(self.width, self.poly, self.init, self.xorout,
+                                              int(bits.data_ptr()) if nframes else None, nframes, ncols - self.width, stride,
+                                              _ptr(ok), _ptr(out) if nframes else None, device,
+                                              _stream_handle(stream, device)), "CRC.check")
+        return out
 
 
 def count_errors(a, b, counts=None, stream=None, device: int = 0):

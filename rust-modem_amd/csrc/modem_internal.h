@@ -395,6 +395,30 @@ struct ViterbiParams {
 };
 // in_dtype: 0 F32, 1 F16, 3 I8
 hipError_t launch_viterbi(const ViterbiParams& p, int in_dtype, hipStream_t s);
+// Rate matching (modem_ratematch.hip), include/modem_hip.h "Rate matching and frame check". mask:
+// bit i is pattern[i]; w its weight; E the kept indices below nm; rows, cl of the interleaver of C
+// columns. tx: in rows of nm bytes, out rows of E bytes; rx: in rows of E elements, out rows of nm
+// (strides in elements). Both set by the caller (capi_ratematch.cpp) from modem_ratematch_math.h.
+struct RmParams {
+    const void* in;
+    void* out;
+    uint64_t nframes, in_stride, out_stride, mask;
+    uint32_t P, w, nm, E, C, rows, cl;
+};
+hipError_t launch_rm_tx(const RmParams& p, hipStream_t s);
+// elem: bytes of a value, 1, 2 or 4
+hipError_t launch_rm_rx(const RmParams& p, int elem, hipStream_t s);
+// The CRC: rows of nbits message bytes (bit 0 of each). attach: out rows of nbits + W bytes;
+// check: in rows of nbits + W bytes, ok_in NULL or nframes bytes, ok_out nframes bytes.
+struct CrcParams {
+    const uint8_t* in;
+    uint8_t* out;                // attach: the rows; check: ok_out
+    const uint8_t* ok_in;
+    uint64_t nframes, in_stride, out_stride;
+    uint32_t nbits, W, poly, init, xorout;
+};
+hipError_t launch_crc_attach(const CrcParams& p, hipStream_t s);
+hipError_t launch_crc_check(const CrcParams& p, hipStream_t s);
 hipError_t launch_phases(float w, uint64_t s0, size_t n, float* out, hipStream_t s);
 hipError_t launch_prng_bits(uint64_t seed, uint8_t* out, size_t nbits, hipStream_t s);
 
